@@ -2,7 +2,13 @@
 """Headline benchmark: depth maps / second on the plane-sweep cost-volume path
 (BASELINE.json: 256x320 images, 96 depth planes, 1 reference + 7 source views), MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg5|cfg3|cfg4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg5|cfg3|cfg4] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `unit`, `ms_per_step`,
+`higher_is_better`, `dtype`, `config`).  `--full` adds everything else the benchmark measures and checks: the exact-fp32
+figures, the per-kernel HIP-event pass and its roofline, the CPU baseline with the parity check against the oracle, and (cfg2,
+one GPU) the other configurations under "extra".  `--dump-outputs DIR` writes what the timed path returned in its last timed
+step as DIR/<name>.npy (float32; inputs are seeded, so two builds can be compared output for output).
 
 `--gpus N` with N > 1 spawns its own N ranks (one process per GPU, torch.distributed / RCCL) when it is not already
 running under torch.distributed.run, so both `python bench.py --gpus 8` and
@@ -18,11 +24,11 @@ Configurations (BASELINE.json `configs`):
         one scene.  cfg4 = cfg3 with the reference views sharded over the ranks and the feature-rich point cloud
         all-gathered over RCCL once per outer iteration (strong scaling of one scene).
 
-The default invocation (cfg2, one GPU) also runs cfg5 (8 views) and the cfg3 scene once each, shorter, and appends their
-figures as compact objects under "extra" (value, ms_per_step, dominant-kernel roofline, depth error against the oracle), so
-that every configuration's number is in the driver-run line; `--no-extra` skips them.
+`--full` at the default configuration (cfg2, one GPU) also runs cfg5 (8 views) and the cfg3 scene once each, shorter, and
+appends their figures as compact objects under "extra" (value, ms_per_step, dominant-kernel roofline, depth error against the
+oracle), so that every configuration's number is in one line; `--no-extra` skips them.
 
-Prints ONE JSON line on rank 0, including
+Prints ONE JSON line on rank 0; with `--full` it also holds
   "value_fp32_exact": the same batch with exact-fp32 MFMA operands (precision='fp32'); `value` uses split-bf16 operands
   "roofline":     achieved vs peak for the dominant kernel (HIP events recorded by the library on the launch stream)
   "cpu_baseline": the oracle (CPU restatement of the reference's PyTorch path) timed on the host cores.
@@ -112,6 +118,27 @@ def cpu_info():
     return model
 
 
+def usable_cpus():
+    """CPUs this process may run on: os.cpu_count() capped by the affinity mask, a cgroup v2 CPU quota and OMP_NUM_THREADS.
+    On a shared host os.cpu_count() is the whole machine's, and thread teams sized by it only oversubscribe the share."""
+    n = os.cpu_count() or 1
+    try:
+        n = min(n, len(os.sched_getaffinity(0)))
+    except (AttributeError, OSError):
+        pass
+    try:
+        quota, period = open('/sys/fs/cgroup/cpu.max').read().split()[:2]
+        if quota != 'max':
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    try:
+        n = min(n, int(os.environ.get('OMP_NUM_THREADS', '')))
+    except ValueError:
+        pass
+    return max(1, n)
+
+
 def _median_time(fn, warmups, runs):
     for _ in range(warmups):
         fn()
@@ -142,14 +169,14 @@ def _oracle_views_job(job):
     return torch.cat(out).numpy()
 
 
-def _oracle_views(cfg, refs, seed, legs, chunk, nt):
+def _oracle_views(cfg, refs, seed, legs, chunk, nt, ncpu=None):
     """Checker legs only (never a timed figure): the oracle's depths of the first n views of the seeded batch for every
     (n, pinned) in `legs`, computed by a few worker processes of `nt` threads each -- torch's CPU kernels stop scaling at
     16-32 threads, the bench host has 256, and the pinned evaluation orders are Python loops.  The workers are spawned (no
     fork of a process that holds a HIP context), rebuild the inputs from the seed and return depth maps only.  Same bits as the
-    in-process loop at `nt` threads (tests/test_driver.py)."""
+    in-process loop at `nt` threads (tests/test_driver.py).  `ncpu`: the CPUs to spread over (default os.cpu_count())."""
     import multiprocessing
-    workers = max(1, min(6, (os.cpu_count() or 1) // (2 * nt)))
+    workers = max(1, min(6, (ncpu or os.cpu_count() or 1) // (2 * nt)))
     jobs, owner = [], []
     for li, (n, pinned) in enumerate(legs):
         parts = max(1, min(workers, (n + chunk - 1) // chunk))
@@ -218,10 +245,11 @@ def bench_costvolume(args, rank, world, dev, dist):
     # The edge list -> per-reference tables (mvsnet.py:179: torch.unique + the scatter grouping) are rebuilt every step, as
     # in the reference's forward -- by the library's device kernel (v3d_edges_csr), which needs the number of reference
     # images of the batch (a property of the batch, `refs` here) instead of reading torch.unique's length back to the host.
-    # Checked once against the torch construction before anything is timed.
-    csr_dev = mvs.edges_to_csr(batch.ref_src_edges, n_ref=refs, n_img=feat.shape[0]).check()
-    csr_ref = mvs.edges_to_csr(batch.ref_src_edges)
-    assert all(torch.equal(a, b) for a, b in zip(csr_dev, csr_ref)), 'device CSR differs from torch.unique + stable sort'
+    # Checked once against the torch construction before anything is timed (`--full`).
+    if args.full:
+        csr_dev = mvs.edges_to_csr(batch.ref_src_edges, n_ref=refs, n_img=feat.shape[0]).check()
+        csr_ref = mvs.edges_to_csr(batch.ref_src_edges)
+        assert all(torch.equal(a, b) for a, b in zip(csr_dev, csr_ref)), 'device CSR differs from torch.unique + stable sort'
 
     def step(precision=None):
         with torch.no_grad():
@@ -234,10 +262,11 @@ def bench_costvolume(args, rank, world, dev, dist):
     launch_mode = 'eager'
     if args.graph:
         try:
-            for prec in (None, 'fp32'):
+            for prec in ((None, 'fp32') if args.full else (None,)):
                 graphs[prec] = mvs.CostVolumeGraph(net, feat, batch, d0, dd, D, inp['plane_size'], n_ref=refs, precision=prec)
-            with torch.no_grad():
-                assert torch.equal(graphs[None].replay(), step(None)), 'graph replay differs from the eager step'
+            if args.full:
+                with torch.no_grad():
+                    assert torch.equal(graphs[None].replay(), step(None)), 'graph replay differs from the eager step'
             launch_mode = 'hip graph (one launch per step)'
         except Exception as e:      # capture unsupported on this stack: time the eager launches
             sys.stderr.write('graph capture failed (%s): timing eager launches\n' % e)
@@ -270,6 +299,27 @@ def bench_costvolume(args, rank, world, dev, dist):
     elapsed, depth = timed(None, args.steps, args.warmup)
     assert torch.isfinite(depth).all()
     value = world * refs * args.steps / elapsed
+    outputs = {'depth': depth.float().cpu()}      # what the timed step returned, for --dump-outputs
+    workload = {
+        'cfg2': 'cfg2: ScanNet-shape 256x320, 1 ref + 7 src (8 edges/ref), 96 planes, 56x56 plane grid, 32-ch quarter '
+                'features 64x80; fused warp+variance -> CostRegNet -> soft-argmin depth (rows A1-A6)',
+        'cfg5': 'cfg5: 480x640, 1 ref + 10 src (11 edges/ref), 192 planes, 120x160 plane grid, 32-ch quarter features '
+                '120x160; fused warp+variance -> CostRegNet -> soft-argmin depth (rows A1-A6)'}[cfg]
+    line = {
+        'metric': 'depth maps/sec (256x320, 96 planes, 7 src)' if cfg == 'cfg2'
+                  else 'depth maps/sec (480x640, 192 planes, 10 src)',
+        'value': value, 'unit': 'depth maps/s', 'n_gpus': world, 'steps': args.steps,
+        'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3,
+        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': DTYPE,
+        'data': 'synthetic',
+        'config': {'workload': workload, 'refs_per_step_per_gpu': refs, 'n_img_per_gpu': inp['n_img'],
+                   'edges_per_ref': inp['edges'].shape[1] // refs,
+                   'parallelism': 'ref-view sharding, no collective' if world > 1 else 'single GPU',
+                   'launch': launch_mode}}
+    if not args.full:
+        line['config']['ranks_seen'] = ranks_seen(args, world, dev, dist)
+        return (line if rank == 0 else None), outputs
+
     # the same batch with exact-fp32 MFMA operands (the reference's arithmetic type), same step count
     elapsed32, depth32 = timed('fp32', args.steps, min(args.warmup, 2))
     value32 = world * refs * args.steps / elapsed32
@@ -302,7 +352,7 @@ def bench_costvolume(args, rank, world, dev, dist):
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import costvolume as ocv   # checker / reported baseline only
         per = inp['edges'].shape[1] // refs
-        ncpu = os.cpu_count() or 1
+        ncpu = usable_cpus()
 
         def cpu_run(v0, v1, pinned=False):
             with torch.no_grad():
@@ -311,7 +361,7 @@ def bench_costvolume(args, rank, world, dev, dist):
                                         inp['plane_size'], pinned=pinned)[0]
         n_s = max(1, min(args.cpu_refs, refs))
         timing = getattr(args, 'cpu_timing', True)      # the "extra" legs only use the oracle as the checker
-        # SURVEY §8d protocol: n = os.cpu_count() threads, 2 warm-ups, median of 5, plus a 1-thread figure.  PyTorch's
+        # SURVEY §8d protocol: n = usable_cpus() threads, 2 warm-ups, median of 5, plus a 1-thread figure.  PyTorch's
         # CPU kernels do not scale to every hardware thread of a big host (256 threads ran 6x SLOWER than one thread
         # on the round-2 box), so a few intermediate counts are probed too (1 view, 1 warm-up, median of 3) and the
         # protocol is repeated at the fastest one: `value` is the best figure (the most favourable to the CPU), `cores`
@@ -345,7 +395,7 @@ def bench_costvolume(args, rank, world, dev, dist):
         n_chk = refs if args.check_refs < 0 else min(args.check_refs, refs)
         chunk = max(1, min(2, n_chk))
         n_host = n_chk if args.host_check_refs < 0 else min(args.host_check_refs, n_chk)
-        d_cpu, d_host = _oracle_views(cfg, refs, seed, [(n_chk, True), (n_host, False)], chunk, min(best_nt, 16))
+        d_cpu, d_host = _oracle_views(cfg, refs, seed, [(n_chk, True), (n_host, False)], chunk, min(best_nt, 16), ncpu)
         d_gpu, d_gpu32 = depth[:n_chk].cpu(), depth32[:n_chk].cpu()
         rel = float(((d_gpu - d_cpu).abs() / d_cpu).max())
         rel32 = float(((d_gpu32 - d_cpu).abs() / d_cpu).max())
@@ -374,18 +424,12 @@ def bench_costvolume(args, rank, world, dev, dist):
                             max_rel_depth_spread_pinned_vs_host_blas_oracle=spread)
 
     if rank != 0:
-        return None
-    e = inp['edges'].shape[1] // refs
-    workload = {
-        'cfg2': 'cfg2: ScanNet-shape 256x320, 1 ref + 7 src (8 edges/ref), 96 planes, 56x56 plane grid, 32-ch quarter '
-                'features 64x80; fused warp+variance -> CostRegNet -> soft-argmin depth (rows A1-A6)',
-        'cfg5': 'cfg5: 480x640, 1 ref + 10 src (11 edges/ref), 192 planes, 120x160 plane grid, 32-ch quarter features '
-                '120x160; fused warp+variance -> CostRegNet -> soft-argmin depth (rows A1-A6)'}[cfg]
+        return None, outputs
+    cfg_line = line['config']
     return {
-        'metric': 'depth maps/sec (256x320, 96 planes, 7 src)' if cfg == 'cfg2'
-                  else 'depth maps/sec (480x640, 192 planes, 10 src)',
+        'metric': line['metric'],
         'value': value, 'value_fp32_exact': value32, 'unit': 'depth maps/s', 'n_gpus': world, 'steps': args.steps,
-        'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3,
+        'warmup': args.warmup, 'ms_per_step': line['ms_per_step'],
         'ms_per_step_fp32_exact': elapsed32 / args.steps * 1e3,
         'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': DTYPE,
         'data': 'synthetic',
@@ -393,11 +437,11 @@ def bench_costvolume(args, rank, world, dev, dist):
                    # (the reference's arithmetic type beside the headline, inside `config` so that a record that keeps only the
                    # contract's keys still carries the VALUES: exact-fp32 MFMA operands, `value` uses split-bf16 x 3)
                    'value_fp32_exact': value32, 'ms_per_step_fp32_exact': elapsed32 / args.steps * 1e3,
-                   'edges_per_ref': e,
-                   'parallelism': 'ref-view sharding, no collective' if world > 1 else 'single GPU',
+                   'edges_per_ref': cfg_line['edges_per_ref'],
+                   'parallelism': cfg_line['parallelism'],
                    'launch': launch_mode,
                    'ranks_seen': n_seen},
-        'roofline': roofline, 'cpu_baseline': cpu_baseline, 'kernels': kernels}
+        'roofline': roofline, 'cpu_baseline': cpu_baseline, 'kernels': kernels}, outputs
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -456,7 +500,7 @@ def bench_scene(args, rank, world, dev, dist):
     # (cost volume: the fp32 chain of cfg2; PointNet / sparse U-Net: v3d_gemm_gather_f32 with V3D_PRECISION_FP32; hypothesis
     # decoder: the unfused interpolation + conv1d chain on fp32 operands -- the fused kernel is split-bf16 only; stage 3: the
     # row-marching PropagationNet kernel on v_mfma_f32_16x16x4_f32).
-    net32 = make_net('fp32') if getattr(args, 'fp32_exact', True) else None
+    net32 = make_net('fp32') if args.full and getattr(args, 'fp32_exact', True) else None
     group = None
 
     def step(n_=None):
@@ -483,6 +527,26 @@ def bench_scene(args, rank, world, dev, dist):
         elapsed = float(tt.item())
     assert torch.isfinite(d).all()
     value = refs * args.steps / elapsed
+    outputs = {'depth': d.float().cpu()}          # what the timed step returned, for --dump-outputs
+    metric = ('depth maps/sec (256x320, 96 planes, full 3DVNet pipeline: cost volume + scene model + 2x3 sweeps%s)'
+              % (' + stage-3 upsampling to 256x320' if stage3 else ''))
+    workload = ('%s: one %d-view scene of the 6x5x3 m box room, 256x320, %d edges/ref (ref-%d .. ref+%d), '
+                '96 planes, 56x56 plane grid, 4 cm voxels; stage A (timed) -> its depths replaced '
+                'by analytic wall depth + 2 cm noise -> 2 x (scene model + 3 point-flow sweeps)%s'
+                % (args.config, refs, nb + na + 1, nb, na,
+                   ' -> stage 3: nearest + PropagationNet at 64x80, 128x160, 256x320 (eval-3dvnet.py:101-125)'
+                   if stage3 else ''))
+    parallelism = ('ref-view sharding + RCCL all-gather of the feature-rich point cloud per outer '
+                   'iteration (the communicating mode)' if world > 1 else 'single GPU')
+    if not args.full:
+        n_seen = ranks_seen(args, world, dev, dist)
+        if rank != 0:
+            return None, outputs
+        return {'metric': metric, 'value': value, 'unit': 'depth maps/s', 'n_gpus': world, 'steps': args.steps,
+                'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True,
+                'scaling': 'strong' if world > 1 else 'weak', 'vs_baseline': None, 'dtype': DTYPE, 'data': 'synthetic',
+                'config': {'workload': workload, 'refs_per_scene': refs, 'refs_per_gpu': refs // world,
+                           'edges_per_ref': nb + na + 1, 'parallelism': parallelism, 'ranks_seen': n_seen}}, outputs
     value32 = ms32 = None
     if net32 is not None:
         steps32 = max(2, args.steps // 2)
@@ -575,7 +639,7 @@ def bench_scene(args, rank, world, dev, dist):
             p_ = p_.double().cpu()
             return torch.floor((p_ - p_.min(0).values) / cfg['edge_len']).long()
         with torch.no_grad():
-            nt = min(32, os.cpu_count() or 1)
+            nt = min(32, usable_cpus())
             torch.set_num_threads(nt)
             onet = OracleNet(sds['cr'], sds['pn'], sds['un'], sds['dec'], cfg['img_size'], cfg['edge_len'], pinned=True)
             # Protocol ("cell flips").  The refinement leg is compared ONE OUTER ITERATION AT A TIME (scene model + 3
@@ -692,12 +756,11 @@ def bench_scene(args, rank, world, dev, dist):
                                              + (' (stage 3 included)' if stage3 else '')),
                       max_abs_refinement_m=float((d_grid - gts).abs().max()))
     if rank != 0:
-        return None
+        return None, outputs
     line_extra = {'stage3': stage3_info} if stage3 and rank == 0 else {}
     return {
         **line_extra,
-        'metric': 'depth maps/sec (256x320, 96 planes, full 3DVNet pipeline: cost volume + scene model + 2x3 sweeps%s)'
-                  % (' + stage-3 upsampling to 256x320' if stage3 else ''),
+        'metric': metric,
         'value': value, 'unit': 'depth maps/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
         'ms_per_step': elapsed / args.steps * 1e3, 'value_fp32_exact': value32, 'ms_per_step_fp32_exact': ms32,
         'higher_is_better': True,
@@ -705,17 +768,11 @@ def bench_scene(args, rank, world, dev, dist):
         'config': {'value_fp32_exact': value32, 'ms_per_step_fp32_exact': ms32,
                    'fp32_exact_note': 'every matrix-core kernel on exact-fp32 operands (the hypothesis decoder as its unfused chain'
                                       + (', stage 3 as the same row-marching kernel on v_mfma_f32_16x16x4_f32)' if stage3 else ')'),
-                   'workload': '%s: one %d-view scene of the 6x5x3 m box room, 256x320, %d edges/ref (ref-%d .. ref+%d), '
-                               '96 planes, 56x56 plane grid, 4 cm voxels; stage A (timed) -> its depths replaced '
-                               'by analytic wall depth + 2 cm noise -> 2 x (scene model + 3 point-flow sweeps)%s'
-                               % (args.config, refs, nb + na + 1, nb, na,
-                                  ' -> stage 3: nearest + PropagationNet at 64x80, 128x160, 256x320 (eval-3dvnet.py:101-125)'
-                                  if stage3 else ''),
+                   'workload': workload,
                    'refs_per_scene': refs, 'refs_per_gpu': refs // world, 'edges_per_ref': nb + na + 1,
-                   'parallelism': ('ref-view sharding + RCCL all-gather of the feature-rich point cloud per outer '
-                                   'iteration (the communicating mode)' if world > 1 else 'single GPU'),
+                   'parallelism': parallelism,
                    'ranks_seen': n_seen, 'collective': collective},
-        'roofline': roofline, 'cpu_baseline': cpu_baseline, 'parity': parity, 'kernels': kernels}
+        'roofline': roofline, 'cpu_baseline': cpu_baseline, 'parity': parity, 'kernels': kernels}, outputs
 
 
 def bench_backbone(dev, n_img=71, iters=10):
@@ -770,6 +827,29 @@ def bench_backbone(dev, n_img=71, iters=10):
             'quarter_features': list(out[1].shape),
             'note': 'parity with torchvision unpinned (absent here); tests/test_backbone.py pins the kernels against oracle/backbone.py '
                     'on the CPU (256x320, 240x320, 248x328): 8e-5 of range split-bf16 (measured <= 4.0e-5), 2e-5 exact fp32'}
+
+
+def leg_done(name, seconds):
+    """`--full`: one stderr line per finished leg (the result line only comes at the end of several minutes)."""
+    sys.stderr.write('bench --full: %s leg done in %.1f s\n' % (name, seconds))
+    sys.stderr.flush()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, outputs, rank, world):
+    """`--dump-outputs DIR`: the arrays the timed path returned in its last timed step, as DIR/<name>.npy in float32 (one
+    file per rank, `<name>_rank<r>.npy`, when N > 1).  An array beyond its share of 64 MB is replaced by a fixed, seeded sample
+    of its flattened elements (same indices every run)."""
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(1, len(outputs) * world)
+    for name, t in outputs.items():
+        a = np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32)
+        if a.nbytes > budget:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, budget // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ('_rank%d' % rank if world > 1 else '') + '.npy'), a)
 
 
 def compact(line):
@@ -926,7 +1006,13 @@ def main():
     ap.add_argument('--extra', action='store_true', help='append the cfg5 / cfg3 figures also when --refs is given')
     ap.add_argument('--dry-run', action='store_true', help='rank plumbing only (gloo, no GPU, no-op step): see bench_dry_run')
     ap.add_argument('--graph', action='store_true', help='time HIP-graph replays of the step instead of eager launches (cfg2 / cfg5)')
+    ap.add_argument('--full', action='store_true', help='also run what the headline does not need: the exact-fp32 figures, the '
+                    'per-kernel pass and roofline, the CPU baseline with the parity check, and (cfg2) the other configurations')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the timed path returned in its last timed '
+                    'step as DIR/<name>.npy (float32)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -947,13 +1033,20 @@ def main():
     if args.config in ('cfg3', 'cfg4'):
         if args.config == 'cfg4' and world == 1:
             print('cfg4 is cfg3 sharded over ranks: run with --gpus N (N > 1); running the 1-GPU scene', file=sys.stderr)
-        line = bench_scene(args, rank, world, dev, dist)
+        line, outputs = bench_scene(args, rank, world, dev, dist)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs, rank, world)
     else:
         t_leg = time.perf_counter()
-        line = bench_costvolume(args, rank, world, dev, dist)
+        line, outputs = bench_costvolume(args, rank, world, dev, dist)
         wall = {'headline': round(time.perf_counter() - t_leg, 1)}
-        if args.config == 'cfg2' and world == 1 and not args.no_extra and (args.extra or not args.refs):
-            # every configuration's figure in the driver-run line: cfg5 (8 views per step) and the cfg3 scene, fewer steps,
+        if args.full:
+            leg_done('headline', wall['headline'])
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs, rank, world)
+        if (args.full and args.config == 'cfg2' and world == 1 and not args.no_extra
+                and (args.extra or not args.refs)):
+            # every configuration's figure in the `--full` line: cfg5 (8 views per step) and the cfg3 scene, fewer steps,
             # the oracle only as the checker (its timing legs belong to the headline configuration)
             import copy
             extra = {}
@@ -961,24 +1054,28 @@ def main():
             a5.config, a5.refs, a5.steps, a5.warmup = 'cfg5', 8, min(args.steps, 10), 2
             a5.check_refs, a5.host_check_refs, a5.cpu_timing, a5.graph = 8, 4, False, False
             t_leg = time.perf_counter()
-            extra['cfg5'] = compact(bench_costvolume(a5, rank, world, dev, dist))
+            extra['cfg5'] = compact(bench_costvolume(a5, rank, world, dev, dist)[0])
             wall['cfg5'] = round(time.perf_counter() - t_leg, 1)
+            leg_done('cfg5', wall['cfg5'])
             t_leg = time.perf_counter()
             a3 = copy.copy(args)
             a3.config, a3.refs, a3.steps, a3.warmup = 'cfg3', 64, min(args.steps, 10), 2
-            extra['cfg3'] = compact(bench_scene(a3, rank, world, dev, dist))
+            extra['cfg3'] = compact(bench_scene(a3, rank, world, dev, dist)[0])
             wall['cfg3'] = round(time.perf_counter() - t_leg, 1)
+            leg_done('cfg3', wall['cfg3'])
             t_leg = time.perf_counter()
             # ... and the same scene with stage 3 (full-resolution output): BASELINE config 3's "Full 3DVNet" end to end
             a3f = copy.copy(a3)
             a3f.stage3, a3f.steps, a3f.cpu_timing, a3f.free_stats = True, min(args.steps, 10), False, False
-            line3f = bench_scene(a3f, rank, world, dev, dist)
+            line3f = bench_scene(a3f, rank, world, dev, dist)[0]
             extra['cfg3_full'] = compact(line3f)
             extra['cfg3_full']['stage3'] = line3f.get('stage3')
             wall['cfg3_full'] = round(time.perf_counter() - t_leg, 1)
+            leg_done('cfg3_full', wall['cfg3_full'])
             t_leg = time.perf_counter()
             extra['backbone'] = bench_backbone(dev)
             wall['backbone'] = round(time.perf_counter() - t_leg, 1)
+            leg_done('backbone', wall['backbone'])
             extra['wall_s_per_leg'] = wall
             # cfg2 from IMAGES: the backbone's batch (71 images = 64 reference views + halo) + the cost-volume step it feeds
             ms_img = extra['backbone']['ms_per_batch'] + line['ms_per_step']

@@ -31,3 +31,19 @@ def golden_costreg_weights(g):
 
 def t(x):
     return torch.from_numpy(np.asarray(x))
+
+
+def pinned_project_to_grid(pts_ref, rotmats, tvecs, K, src_idx, img_size):
+    """oracle.costvolume.project_to_grid with the host-independent evaluation orders of oracle/pinned.py (P = K [R|t] and
+    P [X;1] spelled out with elementwise ops) instead of this host's torch.bmm, whose last bits depend on the host BLAS
+    (MKL with and without FMA differ by one ulp in ~35 % of the coordinates): the goldens' projection on any host."""
+    from oracle import pinned
+    _, P = pinned.camera_blocks(K, rotmats, tvecs)
+    Ps = P[src_idx]                                                       # [E, 3, 4]
+    X = pts_ref.float()                                                   # [E, 3, n_pts]
+    q = [pinned.dot3_chain(Ps[:, i, 0:1], X[:, 0], Ps[:, i, 1:2], X[:, 1], Ps[:, i, 2:3], X[:, 2]) + Ps[:, i, 3:4]
+         for i in range(3)]
+    zb = q[2].abs() + 1e-8
+    gx = ((q[0] / zb) / float(img_size[1] - 1)) * 2 - 1.0
+    gy = ((q[1] / zb) / float(img_size[0] - 1)) * 2 - 1.0
+    return torch.stack((gx, gy), dim=-1).unsqueeze(2)                     # [E, n_pts, 1, 2]

@@ -9,12 +9,15 @@ from helpers import golden_costreg_weights, load_golden, t
 from oracle import costvolume as ocv
 
 
+# The oracle runs with pinned=True: rows A1-A4 in the evaluation orders of the host the goldens were captured on
+# (oracle/pinned.py).  The plain mode's torch.bmm rounds differently with another host BLAS (one ulp of a sample coordinate,
+# up to 2e-5 of variance), so only the pinned mode can meet these tolerances on every host.
 def _run_tiny(g):
     sd = golden_costreg_weights(g)
     d0, dd, D = g['depth_cfg']
     return ocv.mvsnet_depth(t(g['feat']), t(g['rotmats']), t(g['tvecs']), t(g['K']), t(g['edges']),
                             sd, float(d0), float(dd), int(D), tuple(int(v) for v in g['img_size']),
-                            tuple(int(v) for v in g['plane_size']))
+                            tuple(int(v) for v in g['plane_size']), pinned=True)
 
 
 @pytest.mark.parametrize('name', ['A_tiny_flat', 'A_tiny_sharp', 'A_tiny_rotated'])
@@ -22,7 +25,7 @@ def test_oracle_matches_reference_tiny(name):
     g = load_golden(name)
     with torch.no_grad():
         depth, var, reg = _run_tiny(g)
-    # same torch CPU ops as the reference => essentially bit-exact
+    # the reference's torch CPU ops in the golden host's evaluation orders => essentially bit-exact
     np.testing.assert_allclose(var.numpy(), g['var'], rtol=0, atol=1e-6)
     np.testing.assert_allclose(reg.numpy(), g['reg'], rtol=1e-5, atol=1e-5)
     np.testing.assert_allclose(depth.numpy(), g['depth'], rtol=1e-5, atol=0)
@@ -55,7 +58,7 @@ def test_oracle_matches_reference_cfg(name, cfg):
     with torch.no_grad():
         depth, var, reg = ocv.mvsnet_depth(inp['feat'], inp['rotmats'], inp['tvecs'], inp['K'],
                                            inp['edges'], sd, d0, dd, D, inp['img_size'],
-                                           inp['plane_size'])
+                                           inp['plane_size'], pinned=True)
     np.testing.assert_allclose(var[:, ::4, ::3, ::5, ::7].numpy(), g['var_sub'], rtol=0, atol=1e-6)
     assert abs(float(var.double().sum()) - float(g['var_sum'])) < 1e-3
     np.testing.assert_allclose(reg[:, ::3, ::5, ::7].numpy(), g['reg_sub'], rtol=1e-5, atol=1e-5)
@@ -74,7 +77,7 @@ def test_oracle_matches_reference_cfg5():
     with torch.no_grad():
         depth, var, reg = ocv.mvsnet_depth(inp['feat'], inp['rotmats'], inp['tvecs'], inp['K'],
                                            inp['edges'], sd, d0, dd, D, inp['img_size'],
-                                           inp['plane_size'])
+                                           inp['plane_size'], pinned=True)
     np.testing.assert_allclose(var[:, ::4, ::7, ::11, ::13].numpy(), g['var_sub'], rtol=0, atol=1e-6)
     np.testing.assert_allclose(reg[:, ::7, ::11, ::13].numpy(), g['reg_sub'], rtol=1e-5, atol=1e-5)
     np.testing.assert_allclose(depth[:, ::3, ::3].numpy(), g['depth_sub'], rtol=1e-5, atol=0)

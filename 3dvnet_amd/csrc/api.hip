@@ -8,7 +8,7 @@
 
 #include "v3d_common.h"
 
-extern "C" int v3d_version(void) { return 6; }
+extern "C" int v3d_version(void) { return 7; }
 
 extern "C" const char* v3d_last_error(void) { return v3d::err_buf(); }
 
@@ -40,9 +40,8 @@ void timing_end(hipStream_t s) {
 
 namespace {
 struct OptDef { const char* name; int def; };
-const OptDef kOptDefs[v3d::kOptCount] = {{"psv_kernel", 0}, {"psv_threads", 64}, {"c12_march", 1}, {"c12_nseg", 0}, {"c9_kernel", 0},
-                                         {"conv_vec", 1}, {"stop_after", 99}, {"gemm_rounds", 1}, {"gemm_round_rows", 0},
-                                         {"gemm_pipe", 1}, {"tail_streams", 1}, {"tail_from", 3}, {"tail_to", 8}, {"prop_fused", 1}};
+const OptDef kOptDefs[v3d::kOptCount] = {{"psv_kernel", 0}, {"c12_march", 1}, {"stop_after", 99}, {"gemm_rounds", 1},
+                                         {"gemm_pipe", 1}};
 std::atomic<int> g_opt[v3d::kOptCount];
 std::atomic<bool> g_opt_init{false};
 void opt_init() {
@@ -66,10 +65,8 @@ extern "C" int v3d_set_option(const char* name, int value) {
   opt_init();
   for (int i = 0; i < v3d::kOptCount; ++i)
     if (!strcmp(name, kOptDefs[i].name)) {
-#ifndef V3D_EXPERIMENTS
-      V3D_REQUIRE(!(i == v3d::kOptC9Kernel && value == 1), V3D_ERR_UNSUPPORTED,
-                  "v3d_set_option: c9_kernel = 1 (csrc/conv9z.hip) needs a library built with -DV3D_EXPERIMENTS");
-#endif
+      V3D_REQUIRE(!(i == v3d::kOptGemmRounds || i == v3d::kOptGemmPipe) || value == 0 || value == 1, V3D_ERR_BAD_ARG,
+                  "v3d_set_option: %s must be 0 or 1 (got %d)", name, value);
       g_opt[i].store(value);
       return V3D_OK;
     }

@@ -15,9 +15,9 @@
 //     Final depth vs the fp32 CPU oracle: 5e-5 relative (gate 1e-4).
 //
 // (2) The exact-fp32 per-layer kernels (v3d_costreg_layer_f32, and the whole chain with precision = V3D_PRECISION_FP32):
-//     one templated implicit-GEMM kernel on v_mfma_f32_16x16x4_f32 (bitwise an fmaf chain), described below, plus
-//     prob_conv_kernel.  They were the round's first correct path and remain the reference point for the split
-//     kernels' per-layer parity tests.
+//     one templated implicit-GEMM kernel on v_mfma_f32_16x16x4_f32 (bitwise an fmaf chain), described below.  They were
+//     the round's first correct path and remain the reference point for the split kernels' per-layer parity tests; the
+//     chain runs conv9 + skip + prob on the exact-fp32 variant of conv9_prob_kernel.
 //
 //   D[co, voxel] += W'[co, k] * X[k, voxel],  k = (input channel, kernel tap)
 //
@@ -36,10 +36,8 @@
 //     output_padding 1) is decomposed into its 8 output-parity classes, each a dense gather with
 //     1..8 taps (out[o] = sum_k in[(o+1-k)/2] W[k] for (o+1-k) even).
 //
-// The unfused `prob` conv (8 -> 1 channel) is VALU work (a 1-wide GEMM would waste 15/16 of an MFMA)
-// and the depth softmax + expectation is a per-pixel streaming reduction.
+// The depth softmax + expectation is a per-pixel streaming reduction.
 #include <cstdlib>
-#include <mutex>
 #include <type_traits>
 #include <vector>
 
@@ -955,26 +953,20 @@ __global__ __launch_bounds__(64 * NW, 2 * NW / 4) void conv0_bf16x2_kernel(ConvP
 // per-layer kernels that still follow), the split layout (for the next layer of this kind), or both.
 enum { kOutF32 = 1, kOutSplit = 2 };
 
-// FLAT (round 4, PropagationNet): no taps along z -- the "volume" is a stack of independent images [n][C/8][hi, lo][B][H][W]
-// and the layer a batched 3x3 conv2d (upsampling.py:6-11); the weight image then holds the 3 ky fragments only.
-template <int CIN_, int COUT_, int STRIDE_, int WB_, int OUT_, bool FLAT_ = false>
+template <int CIN_, int COUT_, int STRIDE_, int WB_, int OUT_>
 struct CG {
   static constexpr int CIN = CIN_, COUT = COUT_, S = STRIDE_, WB = WB_, OUT = OUT_;
-  static constexpr bool FLAT = FLAT_;
   static constexpr int NCH = CIN / 8, NCG = COUT / 16;
   static constexpr int NRB = 16 / WB;                                  // output rows per MFMA column block
-#ifndef V3D_FLAT_TD
-#define V3D_FLAT_TD 8        // images per tile of the FLAT (conv2d) layers (developer A/B)
-#endif
 #ifndef V3D_CG_TD_S1
 #define V3D_CG_TD_S1 4       // output planes per tile, stride-1 layers at 14-wide rows (developer A/B)
 #endif
 #ifndef V3D_CG_TD_S2
 #define V3D_CG_TD_S2 3       // ... stride-2 layers (2 -> 3: conv1 0.207 -> 0.186 ms, conv3 0.116 -> 0.103; 4 leaves one workgroup per CU: 0.255)
 #endif
-  static constexpr int TD = FLAT ? V3D_FLAT_TD : WB != 14 ? (S == 2 ? 2 : 4) : S == 2 ? V3D_CG_TD_S2 : V3D_CG_TD_S1, TH = 4 * NRB, TW = WB;
-  static constexpr int NKZ = FLAT ? 1 : 3;                             // z taps
-  static constexpr int ID = FLAT ? TD : S * (TD - 1) + 3, IH = S * (TH - 1) + 3, IW = S * (TW - 1) + 3;
+  static constexpr int TD = WB != 14 ? (S == 2 ? 2 : 4) : S == 2 ? V3D_CG_TD_S2 : V3D_CG_TD_S1, TH = 4 * NRB, TW = WB;
+  static constexpr int NKZ = 3;                                     // z taps
+  static constexpr int ID = S * (TD - 1) + 3, IH = S * (TH - 1) + 3, IW = S * (TW - 1) + 3;
   static constexpr int NVOX = ID * IH * IW, NVOXP = NVOX + 8;         // idle lanes read a few slots past a row
   static constexpr int WQ = NKZ * 3 * 2 * 64;                          // 16-byte words of one chunk's weight image
   static constexpr int NVO = TD * TH * TW;
@@ -987,7 +979,7 @@ struct CG {
   // cost a workgroup per CU (conv2: 138 -> 195 VGPRs, 0.20 -> 0.25 ms), so they keep one item per workgroup.
   static constexpr bool PERSIST = NCH == 1;
   static constexpr int OCC = 2;      // (cutting conv2 / conv6 to 128 VGPRs for a fourth workgroup per CU: no gain / slower)
-  static_assert(CIN % 8 == 0 && COUT % 16 == 0 && (WB == 14 || WB == 8) && (!FLAT || S == 1), "shape");
+  static_assert(CIN % 8 == 0 && COUT % 16 == 0 && (WB == 14 || WB == 8), "shape");
   // (the output staging starts at the LDS base: behind the last barrier the weight fragments are as dead as the input tile)
   static_assert((size_t)NVO * 64 <= LDS_BYTES, "split output staging fits in the workgroup's LDS");
   static_assert((size_t)16 * (NVO + 2) * 4 <= LDS_BYTES, "fp32 output staging fits in the workgroup's LDS");
@@ -1045,7 +1037,7 @@ __global__ __launch_bounds__(256, C::OCC) void convg_bf16x2_kernel(ConvGParams p
   u32x4 pre[C::NIT], wreg[C::NWIT];
   constexpr bool XPRE = C::PERSIST;
   auto issue = [&](const Item& q, int chunk) __attribute__((always_inline)) {
-    const int iz0 = C::FLAT ? q.oz0 : C::S * q.oz0 - 1, iy0 = C::S * q.oy0 - 1, sgx = C::S * q.ox0 - 1 + lx;
+    const int iz0 = C::S * q.oz0 - 1, iy0 = C::S * q.oy0 - 1, sgx = C::S * q.ox0 - 1 + lx;
     const bool xin = xok && sgx >= 0 && sgx < p.Wi;
     const int sxc = min(max(sgx, 0), p.Wi - 1);
     // (wave-uniform 64-bit base of the chunk's hi plane + a 32-bit lane offset built from 24-bit multiplies: with size_t
@@ -1126,7 +1118,7 @@ __global__ __launch_bounds__(256, C::OCC) void convg_bf16x2_kernel(ConvGParams p
           const bf16x8 b_lo = __builtin_bit_cast(bf16x8, xs[rowbase + iz * C::IH * C::IW + C::NVOXP]);
 #pragma unroll
           for (int kz = 0; kz < C::NKZ; ++kz) {
-            const int z2 = iz - kz;      // (FLAT: the single tap is the centre one: input plane iz -> output plane iz)
+            const int z2 = iz - kz;
             if (z2 >= 0 && z2 % C::S == 0 && z2 / C::S < C::TD)
               acc[z2 / C::S] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_hi[kz], b_hi, acc[z2 / C::S], 0, 0, 0);
           }
@@ -1407,114 +1399,6 @@ __global__ __launch_bounds__(256, 2) void deconvg_bf16x2_kernel(DeconvGParams p)
           os[(out_plane + sp + 1) * 2] = l1;
         }
       }
-    }
-  }
-}
-
-// ---- prob conv (base -> 1 channel, bias, no BN/ReLU; mvsnet.py:152,162) ---------------------------
-// A 1-channel output would waste 15/16 of an MFMA, so this layer is register-blocked VALU work:
-// a workgroup owns a PT_D x PT_H x (PT_XG*PT_RX) output tile; CK input channels of the halo'd tile
-// are staged in LDS (row stride == 8 (mod 32) floats so the 8 x-groups x 4 rows of a half-wave hit 32
-// distinct banks); each thread produces PT_RX consecutive x outputs from a sliding 9-float window,
-// weights come in through the scalar cache (wave-uniform addresses).
-constexpr int PT_D = 4, PT_H = 8, PT_XG = 8, PT_RX = 7, PT_W = PT_XG * PT_RX;   // 4 x 8 x 56 tile
-constexpr int PT_CK = 2;
-constexpr int PT_ID = PT_D + 2, PT_IH = PT_H + 2, PT_IW = PT_W + 2, PT_RS = 72;
-constexpr int PT_PLANE = PT_ID * PT_IH * PT_RS;
-
-// The halo'd rows are staged as aligned float4s [ox0 - 4, ox0 + 60) -- 16 lanes per row, 16 rows per workgroup instruction
-// round (the regulariser's volumes are multiples of 8 wide, v3d_costreg_depth_f32) -- and the window of an output starts 3
-// floats into the LDS row.  With one float per lane (58 of 64 lanes, 232 bytes per wave instruction at the 4-byte rate of the
-// CU's vector-memory path) the staging loads were the kernel: 0.62 ms per 64 views at cfg2 against 0.1 ms of arithmetic.
-template <int CIN>
-__global__ __launch_bounds__(256) void prob_conv_kernel(const float* __restrict__ in,
-                                                        const float* __restrict__ w,
-                                                        const float* __restrict__ bias,
-                                                        float* __restrict__ out, int n, int D, int H,
-                                                        int W, int ntz, int nty, int ntx) {
-  __shared__ __attribute__((aligned(16))) float xs[PT_CK * PT_PLANE];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int b = v3d::xcd_contiguous_block();     // neighbouring tiles (shared halo) on the same XCD's L2
-  const int tx = b % ntx; b /= ntx;
-  const int ty = b % nty; b /= nty;
-  const int tz = b % ntz;
-  const int bn = b / ntz;
-  const int oz0 = tz * PT_D, oy0 = ty * PT_H, ox0 = tx * PT_W;
-  const size_t plane = (size_t)D * H * W;
-  const float* inb = in + (size_t)bn * CIN * plane;
-
-  // compute role: one z per wave, lane = y * 8 + xg
-  const int cz = wave, cy = lane >> 3, cxg = lane & 7;
-  const int cbase = (cz * PT_IH + cy) * PT_RS + cxg * PT_RX + 3;
-  float acc[PT_RX];
-#pragma unroll
-  for (int i = 0; i < PT_RX; ++i) acc[i] = 0.f;
-
-  constexpr int ROWS = PT_CK * PT_ID * PT_IH;          // 16 lanes per row
-  constexpr int NIT = (ROWS + 15) / 16;
-  static_assert(PT_W % 4 == 0 && PT_RS % 4 == 0 && PT_RS >= 64, "float4 staging");
-  // staging: the next chunk's rows are loaded into registers right after the barrier and stay in flight while the current
-  // chunk is being consumed
-  const int sgx = ox0 - 4 + 4 * (tid & 15);
-  const bool xin = sgx >= 0 && sgx + 3 < W;
-  f32x4 pre[NIT];
-  auto issue = [&](int c0) {
-    int gx_o = sgx;                           // opaque copies keep the per-row address arithmetic from
-    asm volatile("" : "+v"(gx_o));            // being hoisted out of the chunk loop into VGPRs
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int row = it * 16 + (tid >> 4);
-      const int ck = row / (PT_ID * PT_IH), rz = (row / PT_IH) % PT_ID, ry = row % PT_IH;
-      const int gz = oz0 - 1 + rz, gy = oy0 - 1 + ry;
-      const bool ok = row < ROWS && xin && gz >= 0 && gz < D && gy >= 0 && gy < H;
-      const float* src = inb + (size_t)(c0 + ck) * plane + ((size_t)gz * H + gy) * W + gx_o;
-      pre[it] = ok ? *reinterpret_cast<const f32x4*>(src) : (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-  };
-  auto commit = [&]() {
-    int lane_o = 4 * (tid & 15);
-    asm volatile("" : "+v"(lane_o));
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int row = it * 16 + (tid >> 4);
-      const int ck = row / (PT_ID * PT_IH), rz = (row / PT_IH) % PT_ID, ry = row % PT_IH;
-      if (row < ROWS) *reinterpret_cast<f32x4*>(xs + ck * PT_PLANE + (rz * PT_IH + ry) * PT_RS + lane_o) = pre[it];
-    }
-  };
-  issue(0);
-#pragma unroll 1
-  for (int c0 = 0; c0 < CIN; c0 += PT_CK) {
-    __syncthreads();
-    commit();
-    __syncthreads();
-    if (c0 + PT_CK < CIN) issue(c0 + PT_CK);
-#pragma unroll
-    for (int ck = 0; ck < PT_CK; ++ck) {
-#pragma unroll
-      for (int kz = 0; kz < 3; ++kz) {
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-          const float* row = xs + ck * PT_PLANE + cbase + (kz * PT_IH + ky) * PT_RS;
-          float win[PT_RX + 2];
-#pragma unroll
-          for (int i = 0; i < PT_RX + 2; ++i) win[i] = row[i];
-          const float* wk = w + (c0 + ck) * 27 + (kz * 3 + ky) * 3;   // wave-uniform -> s_load
-          const float w0 = wk[0], w1 = wk[1], w2 = wk[2];
-#pragma unroll
-          for (int i = 0; i < PT_RX; ++i) acc[i] += win[i] * w0 + win[i + 1] * w1 + win[i + 2] * w2;
-        }
-      }
-    }
-  }
-  const int gz = oz0 + cz, gy = oy0 + cy;
-  if (gz < D && gy < H) {
-    const float bsv = bias[0];
-    float* o = out + (size_t)bn * plane + ((size_t)gz * H + gy) * W;
-#pragma unroll
-    for (int i = 0; i < PT_RX; ++i) {
-      const int gx = ox0 + cxg * PT_RX + i;
-      if (gx < W) o[gx] = acc[i] + bsv;
     }
   }
 }
@@ -1863,7 +1747,7 @@ __global__ __launch_bounds__(512, 4) void conv9_prob_kernel(C9Params p) {
     const int z = wave >> 1, y = (wave & 1) * 4 + (lane >> 4), xp = lane & 15;
     if (xp < C9::TW / 2) {
       // six accumulation chains (one pair per kz, added at the end) instead of two: a dependent v_pk_fma_f32 costs ~20 cycles
-      // (measured on the depth-march experiment, conv9z.hip, which sums in the same order)
+      // (measured on the retired depth-march experiment of round 4, which summed in the same order)
       f32x2 o0[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}}, o1[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
       const f32x2* wp2 = reinterpret_cast<const f32x2*>(p.wprob);       // [4 pairs][27 taps][2]
 #pragma unroll 1
@@ -2013,7 +1897,7 @@ int launch_conv(const char* name, const float* in, const float* wp, const float*
     v3d::TimedScope ts(name, s);
     // (conv0 only: on conv2 the 40 extra staging registers cost more than the loads save: 0.37 -> 0.41 ms)
     constexpr bool kVecOk = C::MODE == kConvS1Pair && C::PF && C::TW % 4 == 0 && C::IW <= 61;
-    const bool vec = kVecOk && Wi % 4 == 0 && (reinterpret_cast<size_t>(in) & 15) == 0 && v3d::option(v3d::kOptConvVec) != 0;
+    const bool vec = kVecOk && Wi % 4 == 0 && (reinterpret_cast<size_t>(in) & 15) == 0;
     if constexpr (kVecOk) {
       if (vec) conv3d_mfma_kernel<C, true><<<(unsigned)blocks, 256, 0, s>>>(p);
       else conv3d_mfma_kernel<C, false><<<(unsigned)blocks, 256, 0, s>>>(p);
@@ -2152,7 +2036,7 @@ int launch_deconvg(const char* name, const void* in, const float* wbf, const flo
 struct v3d_costreg_weights {
   int in_channels, base;
   float* dev;                 // one allocation holding everything below
-  size_t wp_ofs[10], bias_ofs[10], prob_w_ofs, prob_w2_ofs, prob_b_ofs, c0bf_ofs, c0f32_ofs, cgbf_ofs[7], dgbf_ofs[2], c9bf_ofs, c9f32_ofs, total;
+  size_t wp_ofs[10], bias_ofs[10], prob_w2_ofs, prob_b_ofs, c0bf_ofs, c0f32_ofs, cgbf_ofs[7], dgbf_ofs[2], c9bf_ofs, c9f32_ofs, total;
 };
 
 extern "C" int v3d_costreg_pack(const float* const* conv_w, const float* const* bn_w,
@@ -2369,8 +2253,6 @@ extern "C" int v3d_costreg_pack(const float* const* conv_w, const float* const* 
       for (int t = 0; t < 27; ++t)
         for (int e = 0; e < 2; ++e) host[h->prob_w2_ofs + ((size_t)cp * 27 + t) * 2 + e] = prob_w[(cp * 2 + e) * 27 + t];
   }
-  h->prob_w_ofs = reserve((size_t)base * 27);
-  memcpy(host.data() + h->prob_w_ofs, prob_w, sizeof(float) * base * 27);
   h->prob_b_ofs = reserve(1);
   host[h->prob_b_ofs] = prob_b[0];
   h->total = host.size();
@@ -2464,63 +2346,14 @@ extern "C" int v3d_costreg_layer_split_f32(const v3d_costreg_weights* h, int lay
 // PropagationNet (mv3d/subnetworks/upsampling.py:14-36, stage 3 of eval-3dvnet.py:101-125):
 //   x = cat(features, depth) -> 4 x [conv2d 3x3 p1 + BN + ReLU] (in -> 32 -> 32 -> 32 -> 9) -> softmax over the 9 logits
 //   -> out = sum_k p_k * depth_pad[y + k / 3, x + k % 3]   (replicate padding).
-// The four conv layers run on the FLAT variant of convg_bf16x2_kernel (split-bf16 matrix cores, the image stack as the
-// z axis, split channel-last activations between the layers, BN folded, ReLU in the epilogue); the input is encoded and
-// the softmax + 3x3 propagation applied by the two small kernels below.  Nothing runs on MIOpen / PyTorch.
+// The whole network runs as one row-marching kernel (propz.hip: split-bf16 or exact-fp32 matrix cores, BN folded, ReLU,
+// softmax and the 3x3 propagation in the epilogue).  Nothing runs on MIOpen / PyTorch.
 // ---------------------------------------------------------------------------------------------------------------------
 struct v3d_propagation_weights {
   int in_dim, cinp;
   float* dev;
-  size_t w_ofs[4], b_ofs[4], total;
-  size_t zw_ofs[4], zb_ofs[4], zw32_ofs[4];      // split-bf16 / exact-fp32 fragment images and padded biases of the row-marching kernel (propz.hip)
+  size_t zw_ofs[4], zb_ofs[4], zw32_ofs[4], total;      // split-bf16 / exact-fp32 fragment images and padded biases (propz.hip)
 };
-
-namespace {
-// cat(features [B, Cf, HW], depth [B, HW]) -> split layout [CINP / 8][hi, lo][B * HW] (channels >= Cf + 1 are zero)
-__global__ __launch_bounds__(256) void prop_encode_kernel(const float* __restrict__ feat, const float* __restrict__ depth,
-                                                          u32x4* __restrict__ out, int Cf, int n_grp, size_t HW, size_t N) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= N * n_grp) return;
-  const size_t v = i % N;
-  const int g = (int)(i / N);
-  const size_t img = v / HW, px = v % HW;
-  float x[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int c = g * 8 + e;
-    x[e] = c < Cf ? feat[(img * Cf + c) * HW + px] : c == Cf ? depth[v] : 0.f;
-  }
-  u32x2 ha, la, hb, lb;
-  split4(x[0], x[1], x[2], x[3], ha, la);
-  split4(x[4], x[5], x[6], x[7], hb, lb);
-  out[((size_t)g * 2) * N + v] = (u32x4){ha.x, ha.y, hb.x, hb.y};
-  out[((size_t)g * 2 + 1) * N + v] = (u32x4){la.x, la.y, lb.x, lb.y};
-}
-
-// softmax over the 9 (already ReLU'd) logits of a pixel (upsampling.py:27) and the weighted sum of its replicate-padded 3x3
-// depth neighbourhood in unfold order (:29-36).  logits: [16][B * HW] (channels 9..15 are padding).
-__global__ __launch_bounds__(256) void prop_finish_kernel(const float* __restrict__ logits, const float* __restrict__ depth,
-                                                          float* __restrict__ out, int H, int W, size_t N) {
-  const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (v >= N) return;
-  const size_t HW = (size_t)H * W, img = v / HW;
-  const int y = (int)((v % HW) / W), x = (int)(v % W);
-  float e[9], m = -3.4e38f;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) { e[k] = logits[(size_t)k * N + v]; m = fmaxf(m, e[k]); }
-  float sum = 0.f;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) { e[k] = expf(e[k] - m); sum += e[k]; }
-  const float* const d = depth + img * HW;
-  float acc = 0.f;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    const int yy = min(max(y + k / 3 - 1, 0), H - 1), xx = min(max(x + k % 3 - 1, 0), W - 1);
-    acc += (e[k] / sum) * d[(size_t)yy * W + xx];
-  }
-  out[v] = acc;
-}
-}  // namespace
 
 extern "C" int v3d_propagation_pack(const float* const* conv_weight_host, const float* const* bn_weight_host,
                                     const float* const* bn_bias_host, const float* const* bn_mean_host,
@@ -2536,57 +2369,21 @@ extern "C" int v3d_propagation_pack(const float* const* conv_weight_host, const 
   h->in_dim = in_dim; h->cinp = cinp; h->dev = nullptr;
   std::vector<float> host;
   auto reserve = [&](size_t n) { size_t o = host.size(); host.resize(o + (n + 63) / 64 * 64, 0.f); return o; };
-  auto rne = [](float x) { unsigned u; memcpy(&u, &x, 4); return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16; };
-  auto up = [](unsigned hb) { unsigned u = hb << 16; float f; memcpy(&f, &u, 4); return f; };
-  for (int l = 0; l < 4; ++l) {
-    const int cin = l == 0 ? in_dim : 32, cout = l == 3 ? 9 : 32;
-    const int cp = l == 0 ? cinp : 32, op = l == 3 ? 16 : 32, nch = cp / 8, ncg = op / 16;
-    // [cout group][8-channel chunk][ky][hi, lo][lane 64][4 words]; rows = output channel, k = 8 * x tap + ci (x tap 3 = 0)
-    h->w_ofs[l] = reserve((size_t)ncg * nch * 3 * 2 * 64 * 4);
-    h->b_ofs[l] = reserve(op);
-    unsigned* wb = reinterpret_cast<unsigned*>(host.data() + h->w_ofs[l]);
-    for (int co = 0; co < cout; ++co) {
-      const float sc = bn_weight_host[l][co] / sqrtf(bn_var_host[l][co] + bn_eps);
-      host[h->b_ofs[l] + co] = bn_bias_host[l][co] - bn_mean_host[l][co] * sc;
-    }
-    for (int g = 0; g < ncg; ++g)
-      for (int ch = 0; ch < nch; ++ch)
-        for (int ky = 0; ky < 3; ++ky)
-          for (int lane = 0; lane < 64; ++lane) {
-            const int co = g * 16 + (lane & 15), kx = lane >> 4;
-            unsigned hi[8], lo[8];
-            for (int e = 0; e < 8; ++e) {
-              const int ci = ch * 8 + e;
-              float v = 0.f;
-              if (kx <= 2 && co < cout && ci < cin) {
-                const float sc = bn_weight_host[l][co] / sqrtf(bn_var_host[l][co] + bn_eps);
-                v = conv_weight_host[l][(((size_t)co * cin + ci) * 3 + ky) * 3 + kx] * sc;
-              }
-              hi[e] = rne(v);
-              lo[e] = rne(v - up(hi[e]));
-            }
-            for (int part = 0; part < 2; ++part) {
-              const unsigned* src = part ? lo : hi;
-              unsigned* dst = wb + ((((size_t)g * nch + ch) * 3 + ky) * 2 + part) * 256 + lane * 4;
-              for (int q = 0; q < 4; ++q) dst[q] = src[2 * q] | (src[2 * q + 1] << 16);
-            }
-          }
-  }
-  // the same layers for the row-marching kernel (propz.hip): K step = one tap x 32 input channels (layer 1: (tap, channel)
+  // the layers for the row-marching kernel (propz.hip): K step = one tap x 32 input channels (layer 1: (tap, channel)
   // flattened), BN scale folded, biases padded to whole 16-row blocks
   for (int l = 0; l < 4; ++l) {
     const int cin = l == 0 ? in_dim : 32, cout = l == 3 ? 9 : 32, op = l == 3 ? 16 : 32;
+    h->zw_ofs[l] = reserve(v3d::propz_image_words(l, cinp));
+    h->zb_ofs[l] = reserve(op);
+    h->zw32_ofs[l] = reserve(v3d::propz_image_words(l, cinp));
     std::vector<float> wf((size_t)cout * cin * 9);
     for (int co = 0; co < cout; ++co) {
       const float sc = bn_weight_host[l][co] / sqrtf(bn_var_host[l][co] + bn_eps);
       for (int i = 0; i < cin * 9; ++i) wf[(size_t)co * cin * 9 + i] = conv_weight_host[l][(size_t)co * cin * 9 + i] * sc;
+      host[h->zb_ofs[l] + co] = bn_bias_host[l][co] - bn_mean_host[l][co] * sc;
     }
-    h->zw_ofs[l] = reserve(v3d::propz_image_words(l, cinp));
-    h->zb_ofs[l] = reserve(op);
-    h->zw32_ofs[l] = reserve(v3d::propz_image_words(l, cinp));
     v3d::propz_pack_layer(l, cinp, cin, cout, wf.data(), reinterpret_cast<unsigned*>(host.data() + h->zw_ofs[l]), false);
     v3d::propz_pack_layer(l, cinp, cin, cout, wf.data(), reinterpret_cast<unsigned*>(host.data() + h->zw32_ofs[l]), true);
-    for (int co = 0; co < cout; ++co) host[h->zb_ofs[l] + co] = host[h->b_ofs[l] + co];
   }
   h->total = host.size();
   hipError_t e = hipMalloc((void**)&h->dev, h->total * sizeof(float));
@@ -2603,13 +2400,6 @@ extern "C" void v3d_propagation_free(v3d_propagation_weights* h) {
   delete h;
 }
 
-extern "C" size_t v3d_propagation_workspace_bytes(const v3d_propagation_weights* h, int B, int H, int W) {
-  if (!h || B <= 0 || H <= 0 || W <= 0) return 0;
-  const size_t N = (size_t)B * H * W;
-  // encoded input (cinp channels), two 32-channel activations (ping-pong), 16 logit channels: 4 bytes per value each
-  return v3d::align_up((size_t)h->cinp * N * 4, 256) + 2 * v3d::align_up((size_t)32 * N * 4, 256) + v3d::align_up((size_t)16 * N * 4, 256);
-}
-
 extern "C" int v3d_propagation_up_f32(const v3d_propagation_weights* h, const float* features, const float* depth_lo, int B, int Cf,
                                       int H, int W, int h0, int w0, const int32_t* iy, const int32_t* ix, float* out, int precision,
                                       void* stream) {
@@ -2624,51 +2414,6 @@ extern "C" int v3d_propagation_up_f32(const v3d_propagation_weights* h, const fl
   const float* w[4]; const float* b[4];
   for (int l = 0; l < 4; ++l) { w[l] = h->dev + (f32 ? h->zw32_ofs[l] : h->zw_ofs[l]); b[l] = h->dev + h->zb_ofs[l]; }
   return v3d::launch_propz(h->cinp, f32, features, depth_lo, iy, ix, out, w, b, B, Cf, H, W, h0, w0, (hipStream_t)stream);
-}
-
-extern "C" int v3d_propagation_f32(const v3d_propagation_weights* h, const float* features, const float* depth, int B, int Cf,
-                                   int H, int W, float* out, int precision, void* workspace, size_t workspace_bytes, void* stream) {
-  V3D_REQUIRE(h && features && depth && out && workspace, V3D_ERR_BAD_ARG, "v3d_propagation_f32: null argument");
-  V3D_REQUIRE(precision == V3D_PRECISION_SPLIT_BF16 || precision == V3D_PRECISION_FP32, V3D_ERR_BAD_ARG,
-              "v3d_propagation_f32: unknown precision %d", precision);
-  V3D_REQUIRE(precision == V3D_PRECISION_SPLIT_BF16 || v3d::option(v3d::kOptPropFused) != 0, V3D_ERR_UNSUPPORTED,
-              "v3d_propagation_f32: the per-layer kernels (option prop_fused = 0) have split-bf16 operands only");
-  V3D_REQUIRE(B > 0 && H > 0 && W > 0 && Cf + 1 == h->in_dim, V3D_ERR_BAD_SHAPE,
-              "v3d_propagation_f32: bad shape (B=%d, Cf=%d, H=%d, W=%d; packed for in_dim=%d)", B, Cf, H, W, h->in_dim);
-  V3D_REQUIRE(workspace_bytes >= v3d_propagation_workspace_bytes(h, B, H, W), V3D_ERR_WORKSPACE_TOO_SMALL,
-              "v3d_propagation_f32: workspace %zu < %zu", workspace_bytes, v3d_propagation_workspace_bytes(h, B, H, W));
-  hipStream_t s = (hipStream_t)stream;
-  if (v3d::option(v3d::kOptPropFused) != 0)      // one row-marching kernel, no workspace traffic (propz.hip)
-    return v3d_propagation_up_f32(h, features, depth, B, Cf, H, W, H, W, nullptr, nullptr, out, precision, stream);
-  const size_t N = (size_t)B * H * W;
-  V3D_REQUIRE(N * 5 < ((size_t)1 << 31) * 4, V3D_ERR_BAD_SHAPE, "v3d_propagation_f32: batch too large (chunk the views)");
-  char* base = (char*)workspace;
-  void* enc = base;
-  void* a = base + v3d::align_up((size_t)h->cinp * N * 4, 256);
-  void* b = (char*)a + v3d::align_up((size_t)32 * N * 4, 256);
-  float* logits = (float*)((char*)b + v3d::align_up((size_t)32 * N * 4, 256));
-  {
-    v3d::TimedScope ts("propagation_encode", s);
-    const size_t total = N * (h->cinp / 8);
-    prop_encode_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(features, depth, (u32x4*)enc, Cf, h->cinp / 8, (size_t)H * W, N);
-  }
-  V3D_CHECK_LAUNCH("prop_encode_kernel");
-  auto Wt = [&](int l) { return h->dev + h->w_ofs[l]; };
-  auto Bs = [&](int l) { return h->dev + h->b_ofs[l]; };
-  int rc;
-  if (h->cinp == 8) rc = launch_convg<CG<8, 32, 1, 14, kOutSplit, true>>("propagation_conv1", enc, Wt(0), Bs(0), nullptr, a, 1, B, H, W, s);
-  else if (h->cinp == 24) rc = launch_convg<CG<24, 32, 1, 14, kOutSplit, true>>("propagation_conv1", enc, Wt(0), Bs(0), nullptr, a, 1, B, H, W, s);
-  else rc = launch_convg<CG<40, 32, 1, 14, kOutSplit, true>>("propagation_conv1", enc, Wt(0), Bs(0), nullptr, a, 1, B, H, W, s);
-  if (rc != V3D_OK) return rc;
-  if ((rc = launch_convg<CG<32, 32, 1, 14, kOutSplit, true>>("propagation_conv2", a, Wt(1), Bs(1), nullptr, b, 1, B, H, W, s)) != V3D_OK) return rc;
-  if ((rc = launch_convg<CG<32, 32, 1, 14, kOutSplit, true>>("propagation_conv3", b, Wt(2), Bs(2), nullptr, a, 1, B, H, W, s)) != V3D_OK) return rc;
-  if ((rc = launch_convg<CG<32, 16, 1, 14, kOutF32, true>>("propagation_conv4", a, Wt(3), Bs(3), logits, nullptr, 1, B, H, W, s)) != V3D_OK) return rc;
-  {
-    v3d::TimedScope ts("propagation_softmax_sum", s);
-    prop_finish_kernel<<<(unsigned)((N + 255) / 256), 256, 0, s>>>(logits, depth, out, H, W, N);
-  }
-  V3D_CHECK_LAUNCH("prop_finish_kernel");
-  return V3D_OK;
 }
 
 namespace {
@@ -2732,141 +2477,51 @@ int launch_conv9_prob(bool f32, const v3d_costreg_weights* h, const float* u8, c
   return V3D_OK;
 }
 
-// Side streams of the regulariser's tail (one set per device, created on first use, never destroyed: the library's only
-// device-side resources besides weight handles).  Non-blocking streams; ordering against the caller's stream is by events.
-constexpr int kTailStreamsMax = 8;
-struct TailStreams { hipStream_t st[kTailStreamsMax]; hipEvent_t fork, done[kTailStreamsMax]; int n; };
-TailStreams* tail_streams(int want) {
-  static TailStreams pool[64];
-  static std::mutex mu;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-  std::lock_guard<std::mutex> lk(mu);
-  TailStreams& t = pool[dev];
-  if (t.n == 0 && hipEventCreateWithFlags(&t.fork, hipEventDisableTiming) != hipSuccess) return nullptr;
-  while (t.n < want) {
-    if (hipStreamCreateWithFlags(&t.st[t.n], hipStreamNonBlocking) != hipSuccess) return nullptr;
-    if (hipEventCreateWithFlags(&t.done[t.n], hipEventDisableTiming) != hipSuccess) return nullptr;
-    ++t.n;
-  }
-  return &t;
-}
-
-// The split-bf16 regulariser behind conv0: conv1 + conv2 (step 1), conv3 .. conv8 (steps 3 .. 8), conv9 + skip + prob (9),
-// soft-argmin (10), for views [v0, v0 + nv) on stream st.  Every tensor of the chain is per-view contiguous, so a sub-batch
-// is a pointer offset.
-struct TailCtx {
-  const v3d_costreg_weights* h; WsPlan ws; char* base; const float* depth_vals; float* depth; float* xreg; int n, D, H, W;
-};
-int run_tail_steps(const TailCtx& c, int first, int last, int v0, int nv, hipStream_t st) {
-  const v3d_costreg_weights* h = c.h;
-  const int D = c.D, H = c.H, W = c.W;
-  const size_t V0 = (size_t)D * H * W, V1 = V0 / 8, V2 = V1 / 8, V3 = V2 / 8;
-  auto F = [&](size_t o, size_t per_view) { return (float*)(c.base + o) + (size_t)v0 * per_view; };
+// The split-bf16 regulariser behind conv0, on the caller's stream: conv1 + conv2, conv3 .. conv8, conv9 + skip + prob,
+// soft-argmin.
+int run_split_tail(const v3d_costreg_weights* h, const WsPlan& ws, char* base, const float* depth_vals, int n, int D, int H, int W,
+                   float* depth, float* xreg, hipStream_t s) {
+  const size_t V1 = (size_t)D * H * W / 8;
+  auto F = [&](size_t o) { return (float*)(base + o); };
   // conv1..conv6 hand their activations on in the split layout; the transposed convolutions read their skips (conv2, conv4)
   // from the same split copies (DG::SKIP_SPLIT).  The split copies live in the u9 slot of the workspace, which the fused
   // conv9+prob kernel does not need.
-  float* const c2s_all = (float*)(c.base + c.ws.u9);
-  float* const c4s_all = c2s_all + (size_t)c.n * 16 * V1;
-  float* const c2s = c2s_all + (size_t)v0 * 16 * V1;
-  float* const c4s = c4s_all + (size_t)v0 * 32 * V2;
+  float* const c2s = F(ws.u9);
+  float* const c4s = c2s + (size_t)n * 16 * V1;
   auto W_ = [&](int l) { return h->dev + h->cgbf_ofs[l]; };
   auto B_ = [&](int l) { return h->dev + h->bias_ofs[l]; };
-  int rc;
 #ifdef V3D_PHASE_TIMING
   const int stop_after = v3d::option(v3d::kOptStopAfter);   // isolate one kernel's counters
 #else
   const int stop_after = 99;
 #endif
-  for (int step = first; step <= last; ++step) {
-    if (step > stop_after) return V3D_OK;
-    switch (step) {
-      case 1:
-        // conv1 + conv2: the fused depth march of conv12z.hip (conv1's output never leaves LDS: 0.27 ms per 64 cfg2 views against
-        // 0.176 + 0.146 for the two tile kernels, which remain behind the developer option c12_march = 0 and the per-layer entry points)
-        if (v3d::option(v3d::kOptC12March) != 0) {
-          if ((rc = v3d::launch_conv12z(F(c.ws.c0, 8 * V0), W_(1), W_(2), B_(1), B_(2), c2s, nv, D, H, W, st)) != V3D_OK) return rc;
-        } else {
-          if ((rc = launch_convg<CG<8, 16, 2, 14, kOutSplit>>("costreg_conv1", F(c.ws.c0, 8 * V0), W_(1), B_(1), nullptr, F(c.ws.c1, 16 * V1),
-                                                              nv, D, H, W, st)) != V3D_OK) return rc;
-          if ((rc = launch_convg<CG<16, 16, 1, 14, kOutSplit>>("costreg_conv2", F(c.ws.c1, 16 * V1), W_(2), B_(2), nullptr, c2s, nv, D / 2,
-                                                               H / 2, W / 2, st)) != V3D_OK) return rc;
-        }
-        break;
-      case 3:
-        if ((rc = launch_convg<CG<16, 32, 2, 14, kOutSplit>>("costreg_conv3", c2s, W_(3), B_(3), nullptr, F(c.ws.c3, 32 * V2), nv, D / 2,
-                                                             H / 2, W / 2, st)) != V3D_OK) return rc;
-        break;
-      case 4:
-        if ((rc = launch_convg<CG<32, 32, 1, 14, kOutSplit>>("costreg_conv4", F(c.ws.c3, 32 * V2), W_(4), B_(4), nullptr, c4s, nv, D / 4,
-                                                             H / 4, W / 4, st)) != V3D_OK) return rc;
-        break;
-      case 5:
-        if ((rc = launch_convg<CG<32, 64, 2, 8, kOutSplit>>("costreg_conv5", c4s, W_(5), B_(5), nullptr, F(c.ws.c5, 64 * V3), nv, D / 4,
-                                                            H / 4, W / 4, st)) != V3D_OK) return rc;
-        break;
-      case 6:
-        if ((rc = launch_convg<CG<64, 64, 1, 8, kOutSplit>>("costreg_conv6", F(c.ws.c5, 64 * V3), W_(6), B_(6), nullptr, F(c.ws.c6, 64 * V3),
-                                                            nv, D / 8, H / 8, W / 8, st)) != V3D_OK) return rc;
-        break;
-      case 7:      // conv4 + conv7(x) (mvsnet.py:159)
-        if ((rc = launch_deconvg<DG<64, 32, 8, kOutSplit, true>>("costreg_conv7", F(c.ws.c6, 64 * V3), h->dev + h->dgbf_ofs[0], B_(7), c4s,
-                                                                 nullptr, F(c.ws.u7, 32 * V2), nv, D / 8, H / 8, W / 8, st)) != V3D_OK) return rc;
-        break;
-      case 8:      // conv2 + conv8(x) (:160)
-        if ((rc = launch_deconvg<DG<32, 16, 14, kOutSplit, true>>("costreg_conv8", F(c.ws.u7, 32 * V2), h->dev + h->dgbf_ofs[1], B_(8), c2s,
-                                                                  nullptr, F(c.ws.u8, 16 * V1), nv, D / 4, H / 4, W / 4, st)) != V3D_OK) return rc;
-        break;
-      case 9:
-        // conv9 + skip + prob: the tile kernel.  Developer A/B (v3d_set_option "c9_kernel" = 1): the depth-march experiment of
-        // round 4 (conv9z.hip: correct, but 0.51 against 0.46 ms per 64 views, see its header; -DV3D_EXPERIMENTS builds only)
-        if (v3d::option(v3d::kOptC9Kernel) == 1) {
-          if ((rc = v3d::launch_conv9z(F(c.ws.u8, 16 * V1), F(c.ws.c0, 8 * V0), h->dev + h->c9bf_ofs, h->dev + h->bias_ofs[9],
-                                       h->dev + h->prob_w2_ofs, h->dev + h->prob_b_ofs, c.xreg + (size_t)v0 * V0, nv, D, H, W, st)) != V3D_OK)
-            return rc;
-        } else if ((rc = launch_conv9_prob(false, h, F(c.ws.u8, 16 * V1), F(c.ws.c0, 8 * V0), c.xreg + (size_t)v0 * V0, nv, D, H, W, st)) != V3D_OK) {
-          return rc;
-        }
-        break;
-      case 10:
-        if ((rc = launch_soft_argmin(c.xreg + (size_t)v0 * V0, c.depth_vals, c.depth + (size_t)v0 * H * W, nv, D, H, W, st)) != V3D_OK) return rc;
-        break;
-      default: break;      // step 2: conv2 is part of step 1
-    }
+  int rc = V3D_OK;
+  if (stop_after < 1) return rc;
+  // conv1 + conv2: the fused depth march of conv12z.hip (conv1's output never leaves LDS: 0.27 ms per 64 cfg2 views against
+  // 0.176 + 0.146 for the two tile kernels, which remain behind the developer option c12_march = 0 and the per-layer entry points)
+  if (v3d::option(v3d::kOptC12March) != 0) {
+    rc = v3d::launch_conv12z(F(ws.c0), W_(1), W_(2), B_(1), B_(2), c2s, n, D, H, W, s);
+  } else if ((rc = launch_convg<CG<8, 16, 2, 14, kOutSplit>>("costreg_conv1", F(ws.c0), W_(1), B_(1), nullptr, F(ws.c1), n, D, H, W,
+                                                              s)) == V3D_OK) {
+    rc = launch_convg<CG<16, 16, 1, 14, kOutSplit>>("costreg_conv2", F(ws.c1), W_(2), B_(2), nullptr, c2s, n, D / 2, H / 2, W / 2, s);
   }
-  return V3D_OK;
-}
-
-// Views are independent through the whole regulariser, and the layers behind conv0 are latency-bound rather than
-// throughput-bound (grids of a few hundred short workgroups, 0.04-0.1 ms each: DESIGN.md 8.3).  Steps [tail_from, tail_to]
-// therefore run as `tail_streams` sub-batches of views on the library's side streams -- the kernels of different sub-batches
-// fill each other's ramp-up, drain and barrier gaps -- forked from and joined back into the caller's stream by events
-// (capturable in a HIP graph: a fork / join inside one capture).  Same kernels on the same data: bit-identical results.
-int run_split_tail(const v3d_costreg_weights* h, const WsPlan& ws, char* base, const float* depth_vals, int n, int D, int H, int W,
-                   float* depth, float* xreg, hipStream_t s) {
-  TailCtx c{h, ws, base, depth_vals, depth, xreg, n, D, H, W};
-  int S = v3d::option(v3d::kOptTailStreams);
-  int first = v3d::option(v3d::kOptTailFrom), last = v3d::option(v3d::kOptTailTo);
-  V3D_REQUIRE(S >= 1 && S <= kTailStreamsMax && first >= 1 && first <= 10 && last >= first && last <= 10, V3D_ERR_BAD_ARG,
-              "options tail_streams (1..%d) / tail_from / tail_to (1..10) out of range", kTailStreamsMax);
-  if (S > n) S = n;
-#ifdef V3D_PHASE_TIMING
-  S = 1;
-#endif
-  int rc;
-  if (S == 1) return run_tail_steps(c, 1, 10, 0, n, s);
-  TailStreams* t = tail_streams(S);
-  V3D_REQUIRE(t, V3D_ERR_HIP, "the regulariser's side streams could not be created");
-  if ((rc = run_tail_steps(c, 1, first - 1, 0, n, s)) != V3D_OK) return rc;
-  V3D_CHECK_HIP(hipEventRecord(t->fork, s));
-  for (int k = 0; k < S; ++k) {
-    const int v0 = (int)((long long)n * k / S), v1 = (int)((long long)n * (k + 1) / S);
-    V3D_CHECK_HIP(hipStreamWaitEvent(t->st[k], t->fork, 0));
-    if ((rc = run_tail_steps(c, first, last, v0, v1 - v0, t->st[k])) != V3D_OK) return rc;
-    V3D_CHECK_HIP(hipEventRecord(t->done[k], t->st[k]));
-  }
-  for (int k = 0; k < S; ++k) V3D_CHECK_HIP(hipStreamWaitEvent(s, t->done[k], 0));
-  return run_tail_steps(c, last + 1, 10, 0, n, s);
+  if (rc != V3D_OK || stop_after < 3) return rc;
+  if ((rc = launch_convg<CG<16, 32, 2, 14, kOutSplit>>("costreg_conv3", c2s, W_(3), B_(3), nullptr, F(ws.c3), n, D / 2, H / 2, W / 2,
+                                                       s)) != V3D_OK || stop_after < 4) return rc;
+  if ((rc = launch_convg<CG<32, 32, 1, 14, kOutSplit>>("costreg_conv4", F(ws.c3), W_(4), B_(4), nullptr, c4s, n, D / 4, H / 4, W / 4,
+                                                       s)) != V3D_OK || stop_after < 5) return rc;
+  if ((rc = launch_convg<CG<32, 64, 2, 8, kOutSplit>>("costreg_conv5", c4s, W_(5), B_(5), nullptr, F(ws.c5), n, D / 4, H / 4, W / 4,
+                                                      s)) != V3D_OK || stop_after < 6) return rc;
+  if ((rc = launch_convg<CG<64, 64, 1, 8, kOutSplit>>("costreg_conv6", F(ws.c5), W_(6), B_(6), nullptr, F(ws.c6), n, D / 8, H / 8,
+                                                      W / 8, s)) != V3D_OK || stop_after < 7) return rc;
+  // conv4 + conv7(x) (mvsnet.py:159)
+  if ((rc = launch_deconvg<DG<64, 32, 8, kOutSplit, true>>("costreg_conv7", F(ws.c6), h->dev + h->dgbf_ofs[0], B_(7), c4s, nullptr,
+                                                           F(ws.u7), n, D / 8, H / 8, W / 8, s)) != V3D_OK || stop_after < 8) return rc;
+  // conv2 + conv8(x) (:160)
+  if ((rc = launch_deconvg<DG<32, 16, 14, kOutSplit, true>>("costreg_conv8", F(ws.u7), h->dev + h->dgbf_ofs[1], B_(8), c2s, nullptr,
+                                                            F(ws.u8), n, D / 4, H / 4, W / 4, s)) != V3D_OK || stop_after < 9) return rc;
+  if ((rc = launch_conv9_prob(false, h, F(ws.u8), F(ws.c0), xreg, n, D, H, W, s)) != V3D_OK || stop_after < 10) return rc;
+  return launch_soft_argmin(xreg, depth_vals, depth, n, D, H, W, s);
 }
 }  // namespace
 
@@ -2927,7 +2582,7 @@ static int costreg_depth_impl(int in_layout, const v3d_costreg_weights* h, const
                                      W, s)) != V3D_OK) return rc;
       }
     }
-    // conv1 .. conv9 + prob, soft-argmin: see run_split_tail() below (sub-batches of views on concurrent streams)
+    // conv1 .. conv9 + prob, soft-argmin
     return run_split_tail(h, ws, base, depth_vals, n, D, H, W, depth, xreg, s);
   }
   RUN(3, F(ws.c2), nullptr, F(ws.c3), D / 2, H / 2, W / 2);
@@ -2936,20 +2591,8 @@ static int costreg_depth_impl(int in_layout, const v3d_costreg_weights* h, const
   RUN(6, F(ws.c5), nullptr, F(ws.c6), D / 8, H / 8, W / 8);
   RUN(7, F(ws.c6), F(ws.c4), F(ws.u7), D / 8, H / 8, W / 8);    // conv4 + conv7(x)  (mvsnet.py:159)
   RUN(8, F(ws.u7), F(ws.c2), F(ws.u8), D / 4, H / 4, W / 4);    // conv2 + conv8(x)  (:160)
-  // conv9 + skip + prob on exact-fp32 operands: the tile kernel; developer A/B (v3d_set_option "c9_kernel" = 2): the per-layer
-  // conv9 kernel + prob_conv_kernel (rounds 1-3)
-  if (v3d::option(v3d::kOptC9Kernel) != 2) {
-    if ((rc = launch_conv9_prob(true, h, F(ws.u8), F(ws.c0), xreg, n, D, H, W, s)) != V3D_OK) return rc;
-  } else {
-    RUN(9, F(ws.u8), F(ws.c0), F(ws.u9), D / 2, H / 2, W / 2);    // conv0 + conv9(x)  (:161)
-    {
-      v3d::TimedScope ts("costreg_prob", s);
-      const int ntz = (D + PT_D - 1) / PT_D, nty = (H + PT_H - 1) / PT_H, ntx = (W + PT_W - 1) / PT_W;
-      prob_conv_kernel<8><<<(unsigned)((size_t)n * ntz * nty * ntx), 256, 0, s>>>(      // W % 8 == 0 (checked above)
-          F(ws.u9), h->dev + h->prob_w_ofs, h->dev + h->prob_b_ofs, xreg, n, D, H, W, ntz, nty, ntx);
-    }
-    V3D_CHECK_LAUNCH("prob_conv_kernel");
-  }
+  // conv9 + skip + prob on exact-fp32 operands: the tile kernel
+  if ((rc = launch_conv9_prob(true, h, F(ws.u8), F(ws.c0), xreg, n, D, H, W, s)) != V3D_OK) return rc;
 #undef RUN
   return launch_soft_argmin(xreg, depth_vals, depth, n, D, H, W, s);
 }

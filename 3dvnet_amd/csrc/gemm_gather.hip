@@ -649,9 +649,9 @@ struct StepIter {
 #define V3D_PIPE_ABLATE 0     // developer ablations (scripts/micro/sparse_ablate.sh): 1 no MFMAs, 2 no fragment loads, 3 no gathers, 4 no split / LDS writes
 #endif
 // NL: loader waves (4 or 8); AD: depth of the weight-fragment ring of the matrix waves (fragments of AD - 1 rounds in flight)
-template <int MBW, int NB, int NL, int AD, int MINB>
+template <int MBW, int NB, int NL, int MINB>
 __global__ __launch_bounds__(256 + 64 * NL, MINB) void gemm_gather_pipe_kernel(GemmParams p) {
-  constexpr int kTM = 16 * NB, MB = 4 * MBW, S = 2, U = 4, NT = 256 + 64 * NL;
+  constexpr int kTM = 16 * NB, MB = 4 * MBW, S = 2, U = 4, NT = 256 + 64 * NL, AD = 2;
   constexpr int RPP = NL * 8;                       // rows per loader pass: 8 threads x 16 B = one 128-byte row slice
   constexpr int NPASS = (kTM + RPP - 1) / RPP;
   constexpr int kWslab = 4 * MBW * 16 * kKC;        // packed floats per (segment, K chunk)
@@ -1130,8 +1130,8 @@ extern "C" int v3d_gemm_gather_f32(const v3d_gemm_weights* h, int M, const float
     else gemm_gather_kernel<MBW_, NB_, true><<<blocks, 256, 0, s>>>(p);                    \
   } while (0)
     // small M, split-bf16, every segment 16-byte loadable: the rounds kernel (four steps per pair of barriers)
-    const int rounds_opt = v3d::option(v3d::kOptGemmRounds);
-    bool rounds = (small || rounds_opt == 2) && !fp32_path && h->K % 4 == 0 && h->n_seg * (h->KP / kKC) >= 2 && h->KP / kKC <= 8 && rounds_opt != 0;
+    bool rounds = small && !fp32_path && h->K % 4 == 0 && h->n_seg * (h->KP / kKC) >= 2 && h->KP / kKC <= 8 &&
+                  v3d::option(v3d::kOptGemmRounds) != 0;
     for (int t = 0; rounds && t < h->n_seg; ++t)
       rounds = p.seg[t].ld % 4 == 0 && (reinterpret_cast<size_t>(p.seg[t].src) & 15) == 0;
     // a sparse convolution (one source, a row map per offset): the loader / matrix pipeline
@@ -1143,57 +1143,22 @@ extern "C" int v3d_gemm_gather_f32(const v3d_gemm_weights* h, int M, const float
       // rows per tile: a tile streams the whole weight image through its CU's vector-memory path (27 x K x N x 4 bytes), so
       // the tile is as tall as the number of workgroups allows -- about one per CU on the 128-channel levels, two on the wide
       // 64-channel level
-      const int rows_opt = v3d::option(v3d::kOptGemmRoundRows);
-      V3D_REQUIRE(rows_opt == 0 || rows_opt == 32 || rows_opt == 64 || rows_opt == 128, V3D_ERR_BAD_ARG,
-                  "option gemm_round_rows must be 0, 32, 64 or 128 (got %d)", rows_opt);
-      const int rows = rows_opt ? rows_opt : (h->MBW == 2 ? (M >= 8192 ? 64 : 32) : (M >= 8192 ? 64 : 32));
-      const unsigned rb = (unsigned)((M + rows - 1) / rows);
-      // measured on the cfg3 scene's levels (scripts/micro/sparse_ab.sh; rounds kernel -> here): 13 434 rows x 128 channels 84 -> 60 us
-      // with 64-row tiles and 8 loader waves, 2 719 x 128: 58 -> 40 us with 32-row tiles and 4 loader waves, 59 975 x 64: 90 -> 84 us;
-      // option gemm_pipe = 2 is the first version of the kernel (4 loader waves, fragments of 3 rounds in flight) for A/B runs
-      const bool v2 = v3d::option(v3d::kOptGemmPipe) == 2;
-#define V3D_PIPE(MBW_, NB_, NL_, MINB_)                                                                          \
-  do {                                                                                                           \
-    if (v2) gemm_gather_pipe_kernel<MBW_, NB_, 4, 4, 1><<<rb, 512, 0, s>>>(p);                                   \
-    else gemm_gather_pipe_kernel<MBW_, NB_, NL_, 2, MINB_><<<rb, 256 + 64 * NL_, 0, s>>>(p);                     \
-  } while (0)
+      // measured on the cfg3 scene's levels (rounds kernel -> here): 13 434 rows x 128 channels 84 -> 60 us with 64-row tiles and
+      // 8 loader waves, 2 719 x 128: 58 -> 40 us with 32-row tiles and 4 loader waves, 59 975 x 64: 90 -> 84 us
+      const bool tall = M >= 8192;
+      const unsigned rb = (unsigned)((M + (tall ? 63 : 31)) / (tall ? 64 : 32));
       if (h->MBW == 2) {
-        if (rows == 128) V3D_PIPE(2, 8, 8, 1);
-        else if (rows == 64) V3D_PIPE(2, 4, 8, 1);
-        else V3D_PIPE(2, 2, 4, 2);
+        if (tall) gemm_gather_pipe_kernel<2, 4, 8, 1><<<rb, 768, 0, s>>>(p);
+        else gemm_gather_pipe_kernel<2, 2, 4, 2><<<rb, 512, 0, s>>>(p);
       } else {
-        if (rows == 128) V3D_PIPE(1, 8, 8, 1);
-        else if (rows == 64) V3D_PIPE(1, 4, 8, 1);
-        else V3D_PIPE(1, 2, 4, 2);
+        if (tall) gemm_gather_pipe_kernel<1, 4, 8, 1><<<rb, 768, 0, s>>>(p);
+        else gemm_gather_pipe_kernel<1, 2, 4, 2><<<rb, 512, 0, s>>>(p);
       }
-#undef V3D_PIPE
     } else if (rounds) {
-      // developer A/B: rows per tile (32 / 64 / 128) -- a tile re-reads the whole weight image, so L2 -> CU weight traffic is
-      // M / rows x 27 x K x N x 4 bytes (0.8 GB per 64-channel conv on 60 k voxels with 32-row tiles, twice the gathers)
-      const int rows_env = v3d::option(v3d::kOptGemmRoundRows);
-      V3D_REQUIRE(rows_env == 0 || rows_env == 32 || rows_env == 64 || rows_env == 128, V3D_ERR_BAD_ARG,
-                  "option gemm_round_rows must be 0, 32, 64 or 128 (got %d)", rows_env);
-      const int rows = rows_env ? rows_env : small ? 32 : 128;
-      const unsigned rb = (unsigned)((M + rows - 1) / rows);
-      if (h->MBW == 2) {
-        if (rows == 128) gemm_gather_rounds_kernel<2, 8, 2><<<rb, 256, 0, s>>>(p);
-        else if (rows == 64) gemm_gather_rounds_kernel<2, 4, 4><<<rb, 256, 0, s>>>(p);
-        else gemm_gather_rounds_kernel<2, 2, 4><<<rb, 256, 0, s>>>(p);
-      } else {
-        if (rows == 128) gemm_gather_rounds_kernel<1, 8, 2><<<rb, 256, 0, s>>>(p);
-        else if (rows == 64) gemm_gather_rounds_kernel<1, 4, 4><<<rb, 256, 0, s>>>(p);
-        else gemm_gather_rounds_kernel<1, 2, 4><<<rb, 256, 0, s>>>(p);
-      }
-    } else if (!small && v3d::option(v3d::kOptGemmRoundRows) == 64) {
-      // developer A/B: 64-row tiles for large M on the one-step kernel (half the accumulators, one more workgroup per CU)
-      const unsigned b64 = (unsigned)((M + 63) / 64);
-#define V3D_GG64(MBW_)                                                                     \
-  do {                                                                                     \
-    if (fp32_path) gemm_gather_kernel<MBW_, 4, false><<<b64, 256, 0, s>>>(p);              \
-    else gemm_gather_kernel<MBW_, 4, true><<<b64, 256, 0, s>>>(p);                         \
-  } while (0)
-      if (h->MBW == 2) V3D_GG64(2); else V3D_GG64(1);
-#undef V3D_GG64
+      // 32-row tiles: a tile re-reads the whole weight image, so L2 -> CU weight traffic is M / 32 x 27 x K x N x 4 bytes
+      const unsigned rb = (unsigned)((M + 31) / 32);
+      if (h->MBW == 2) gemm_gather_rounds_kernel<2, 2, 4><<<rb, 256, 0, s>>>(p);
+      else gemm_gather_rounds_kernel<1, 2, 4><<<rb, 256, 0, s>>>(p);
     } else if (h->MBW == 2) { if (small) V3D_GG(2, 2); else V3D_GG(2, 8); }
     else { if (small) V3D_GG(1, 2); else V3D_GG(1, 8); }
 #undef V3D_GG

@@ -3,8 +3,8 @@
 // logits, convex combination of the replicate-padded 3x3 depth neighbourhood), applied after a nearest-neighbour resize of the
 // depth (mv3d/eval-3dvnet.py:101-125).
 //
-// The per-layer path (costreg.hip: prop_encode_kernel + 4 x convg_bf16x2_kernel<FLAT> + prop_finish_kernel) writes and re-reads
-// a 32-channel activation tensor per layer: 0.67 GB each at 256 x 320 x 64 views, 6.2 GB per scene, and spends a quarter of its
+// The retired per-layer path of round 4 (an encode kernel + four split-bf16 conv launches + a softmax kernel) wrote and re-read
+// a 32-channel activation tensor per layer: 0.67 GB each at 256 x 320 x 64 views, 6.2 GB per scene, and spent a quarter of its
 // matrix instructions on a zero x tap (K = 4 x taps x 8 channels).  Here a workgroup owns a 40-column strip of one image and
 // marches down its rows; the activations of the four layers live in LDS as rings of four rows and never reach HBM:
 //

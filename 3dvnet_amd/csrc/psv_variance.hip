@@ -216,13 +216,12 @@ __device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_){a, b}, psv_bf16x2));
 }
 
-// THREADS = 64: one wave per workgroup (16 pixels x 4 planes).  The projection, gather and store phases of a
-// workgroup are separated by barriers; with single-wave workgroups the barriers are free and the 24 resident
-// waves of a CU drift apart, so the L1 (the binding resource, busy only during the gather phase) always has some
-// wave gathering.
-template <int C, bool SPLIT, int THREADS>
-__global__ __launch_bounds__(THREADS) void psv_variance_kernel(PsvParams p) {
-  constexpr int kThreads = THREADS, kPix = THREADS / 4;
+// One wave per workgroup (16 pixels x 4 planes).  The projection, gather and store phases of a workgroup are separated
+// by barriers; with single-wave workgroups the barriers are free and the 24 resident waves of a CU drift apart, so the L1
+// (the binding resource, busy only during the gather phase) always has some wave gathering.
+template <int C, bool SPLIT>
+__global__ __launch_bounds__(64) void psv_variance_kernel(PsvParams p) {
+  constexpr int kThreads = 64, kPix = kThreads / 4;
   constexpr int LP = C / 4;               // lanes per pixel
   constexpr int PPP = kThreads / LP;      // pixels per phase-2 pass
   constexpr int NPASS = kPix / PPP;
@@ -1103,11 +1102,8 @@ static int psv_variance_impl(int mode, const float* feat, const float* K, const 
   p.ref_img = ref_img; p.edge_ofs = edge_ofs; p.edge_src = edge_src; p.var = var; p.camp = camp;
   p.n_img = n_img; p.n_ref = n_ref; p.Hf = Hf; p.Wf = Wf; p.H = H; p.W = W; p.D = D;
   p.h = h; p.w = w;
-  // workgroup size: single-wave workgroups (16 pixels) unless the developer option psv_threads = 256 asks for the 64-pixel variant
-  const int threads = v3d::option(v3d::kOptPsvThreads);
-  V3D_REQUIRE(threads == 64 || threads == 256, V3D_ERR_BAD_ARG, "option psv_threads must be 64 or 256");
-  const int pix = threads / 4;
-  p.n_ptile = (h * w + pix - 1) / pix;
+  // single-wave workgroups of 16 pixels
+  p.n_ptile = (h * w + 15) / 16;
   p.x_step = w > 1 ? (double)(W - 1) / (double)(w - 1) : 0.0;
   p.y_step = h > 1 ? (double)(H - 1) / (double)(h - 1) : 0.0;
   const double depth_end = depth_start + (double)(D - 1) * depth_interval;
@@ -1120,11 +1116,6 @@ static int psv_variance_impl(int mode, const float* feat, const float* K, const 
   {
     v3d::TimedScope ts("psv_variance", s);
     const unsigned grid = (unsigned)blocks;
-#define V3D_PSV(C_, SPLIT_)                                                        \
-  do {                                                                             \
-    if (threads == 64) psv_variance_kernel<C_, SPLIT_, 64><<<grid, 64, 0, s>>>(p); \
-    else psv_variance_kernel<C_, SPLIT_, 256><<<grid, 256, 0, s>>>(p);             \
-  } while (0)
     const int psv_kernel = v3d::option(v3d::kOptPsvKernel);     // developer A/B (v3d_set_option): 0 auto, 1 reuse, 2 gather kernel
     const bool plain_gather = psv_kernel == 2;
     if (C == 32 && !plain_gather) {
@@ -1159,10 +1150,9 @@ static int psv_variance_impl(int mode, const float* feat, const float* K, const 
       }
     } else if (cl8) {
       return v3d::fail(V3D_ERR_UNSUPPORTED, "v3d_psv_variance_cl8: C=%d unsupported (32) / option psv_kernel = 2", C);
-    } else if (split) V3D_PSV(32, true);
-    else if (C == 32) V3D_PSV(32, false);
-    else V3D_PSV(16, false);
-#undef V3D_PSV
+    } else if (split) psv_variance_kernel<32, true><<<grid, 64, 0, s>>>(p);
+    else if (C == 32) psv_variance_kernel<32, false><<<grid, 64, 0, s>>>(p);
+    else psv_variance_kernel<16, false><<<grid, 64, 0, s>>>(p);
   }
   V3D_CHECK_LAUNCH("psv_variance_kernel");
   return V3D_OK;

@@ -49,19 +49,10 @@ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // variables earlier rounds read on the launch paths; none of them is needed in production, every default is the shipped path.
 enum Option {
   kOptPsvKernel,       // "psv_kernel": 0 auto (window kernel; reuse kernel for feature stacks >= 2 GB), 1 reuse kernel, 2 gather kernel
-  kOptPsvThreads,      // "psv_threads": 64 | 256, workgroup size of the gather kernel
   kOptC12March,        // "c12_march": 1 conv1 + conv2 as one depth march (conv12z.hip), 0 the two tile kernels
-  kOptC12Nseg,         // "c12_nseg": 0 auto, else z segments per tile of the conv1 + conv2 march
-  kOptC9Kernel,        // "c9_kernel": 0 tile kernel, 1 depth-march experiment (builds with -DV3D_EXPERIMENTS only), 2 exact-fp32 unfused
-  kOptConvVec,         // "conv_vec": 1 float4 staging of halo rows in the exact-fp32 layer kernel, 0 scalar
   kOptStopAfter,       // "stop_after": regulariser returns after this layer (-DV3D_PHASE_TIMING builds: isolates a kernel's counters)
-  kOptGemmRounds,      // "gemm_rounds": 1 gather-GEMM in rounds for small M, 0 the one-step kernel, 2 rounds for every M (measured: PointNet's 200 k-row layers 1.25 -> 1.21 ms per scene, not the default)
-  kOptGemmRoundRows,   // "gemm_round_rows": 0 auto, 32 | 64 | 128 rows per tile of the rounds / pipeline kernel
-  kOptGemmPipe,        // "gemm_pipe": 1 sparse convolutions on the loader / matrix pipeline kernel (2: its first version), 0 the rounds kernel
-  kOptTailStreams,     // "tail_streams": sub-batches of views the regulariser's layers behind conv0 run in, on concurrent side streams (1 = the caller's stream only)
-  kOptTailFrom,        // "tail_from": first step of the concurrent section (1 conv1 + conv2, 3 .. 8 conv3 .. conv8, 9 conv9 + prob, 10 soft-argmin)
-  kOptTailTo,          // "tail_to": last step of the concurrent section
-  kOptPropFused,       // "prop_fused": 1 PropagationNet as one row-marching kernel (propz.hip), 0 the per-layer kernels (encode + 4 conv + finish)
+  kOptGemmRounds,      // "gemm_rounds": 1 gather-GEMM in rounds for small M, 0 the one-step kernel
+  kOptGemmPipe,        // "gemm_pipe": 1 sparse convolutions on the loader / matrix pipeline kernel, 0 the rounds kernel
   kOptCount
 };
 int option(Option o);
@@ -229,12 +220,6 @@ __device__ __forceinline__ void sample_position(const float* Pm, float X, float 
 // `wimg` = the fp32 fragment image (c0f32).
 int launch_conv0z(bool f32, const void* in, const float* wimg, const float* bias, void* out, int n, int D, int H, int W,
                   hipStream_t s);
-
-// conv9 + conv0 skip + prob of CostRegNet as a depth march (conv9z.hip): u8 [n][2][hi, lo][D/2][H/2][W/2] and the conv0 skip
-// [n][hi, lo][D][H][W] (split layouts) -> x_reg [n, D, H, W]; `wbf` = the split-bf16 image of conv9 (costreg.hip, c9bf),
-// `wprob` = the pair-interleaved prob weights
-int launch_conv9z(const void* u8_split, const void* c0_split, const float* wbf, const float* bias9, const float* wprob,
-                  const float* bprob, float* out, int n, int D, int H, int W, hipStream_t s);
 
 // conv1 + conv2 of CostRegNet as one depth march (conv12z.hip, experiment): conv0 output [n][hi, lo][D][H][W] (split layout)
 // -> conv2 output [n][2 groups][hi, lo][D2][H2][W2]; `w1` / `w2` = the split-bf16 images of conv1 / conv2 (costreg.hip, cgbf)

@@ -2,7 +2,7 @@
 ``mv3d/eval-3dvnet.py:101-125``.  Host-side mirror of ``mv3d/subnetworks/upsampling.py::PropagationNet``: same
 constructor, ``forward(features, depth)`` signature and ``state_dict`` keys (``conv{1..4}.{0.weight,1.*}``).
 
-The arithmetic runs in the HIP library (``v3d_propagation_f32`` / ``v3d_propagation_up_f32``, csrc/propz.hip): ONE launch
+The arithmetic runs in the HIP library (``v3d_propagation_up_f32``, csrc/propz.hip): ONE launch
 per net marches down the image rows with one wave per layer -- the four 3x3 convolutions on matrix cores (split-bf16 or
 exact fp32 operands) with eval-mode BatchNorm folded and ReLU in the epilogue, the activations between the layers in
 LDS rings of four rows, then the 9-way softmax and the weighted sum over the replicate-padded 3x3 depth neighbourhood
@@ -17,7 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .mvsnet import _Workspace, module_state_key
+from .mvsnet import module_state_key
 
 
 def _stage(c_in, c_out):
@@ -39,7 +39,6 @@ class PropagationNet(nn.Module):
         for i in range(4):
             setattr(self, 'conv%d' % (i + 1), _stage(widths[i], widths[i + 1]))
         self._handle, self._packed_key = None, None
-        self._ws = _Workspace()
 
     def packed_handle(self, device):
         key = (str(device),) + module_state_key(self)
@@ -97,18 +96,11 @@ class PropagationNet(nn.Module):
         depth = depth.contiguous().float()
         B, Cf, H, W = features.shape
         assert depth.shape == (B, 1, H, W) and Cf + 1 == self.in_dim, (tuple(depth.shape), tuple(features.shape), self.in_dim)
-        handle = self.packed_handle(dev)
         out = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-        # the conv kernels address a launch's image stack with 32-bit slot offsets (B * H * W < 2^24 slots, checked by the
-        # library): larger stacks go through in pieces -- images are independent, the result is the same bit for bit
-        step = max(1, ((1 << 24) - 1) // (H * W))
-        for s in range(0, B, step):
-            nb = min(step, B - s)
-            ws = self._ws.get('prop', lib.v3d_propagation_workspace_bytes(handle, nb, H, W), dev)
-            rc = lib.v3d_propagation_f32(handle, features[s:s + nb].data_ptr(), depth[s:s + nb].data_ptr(), nb, Cf, H, W,
-                                         out[s:s + nb].data_ptr(), _lib.precision_code(self.precision), ws.data_ptr(), ws.numel(),
-                                         _lib.stream_ptr(dev))
-            _lib.check(rc, 'v3d_propagation_f32')
+        # no resize: null index tables with a depth of the output size
+        rc = lib.v3d_propagation_up_f32(self.packed_handle(dev), features.data_ptr(), depth.data_ptr(), B, Cf, H, W, H, W, None, None,
+                                        out.data_ptr(), _lib.precision_code(self.precision), _lib.stream_ptr(dev))
+        _lib.check(rc, 'v3d_propagation_up_f32')
         return out
 
     def forward_resized(self, features, depth_lo):

@@ -50,22 +50,11 @@ extern "C" {
 /* Developer options: process-wide integers the launch paths read (they replace the environment variables of earlier rounds; a
  * production caller never needs them -- every default is the shipped path).  Names / values:
  *   "psv_kernel"      0 auto (window kernel; reuse kernel for feature stacks >= 2 GB) | 1 reuse kernel | 2 gather kernel
- *   "psv_threads"     64 | 256   workgroup size of the gather kernel
  *   "c12_march"       1 conv1 + conv2 of CostRegNet as one depth march | 0 the two tile kernels (another summation order of conv2)
- *   "c12_nseg"        0 auto | z segments per tile of that march
- *   "c9_kernel"       0 tile kernel | 1 depth-march experiment (libraries built with -DV3D_EXPERIMENTS only) | 2 exact-fp32 unfused
- *   "conv_vec"        1 | 0      float4 staging in the exact-fp32 per-layer kernel
  *   "stop_after"      layer after which v3d_costreg_depth_* returns (-DV3D_PHASE_TIMING builds)
- *   "gemm_rounds"     1 | 0 | 2  gather-GEMM in rounds for small M | the one-step kernel | rounds for every M (bit-identical)
- *   "gemm_round_rows" 0 auto | 32 | 64 | 128
- *   "gemm_pipe"       1 | 2 | 0  sparse convolutions on the loader / matrix pipeline kernel (2: its first version) | the rounds kernel;
- *                                bit-identical to each other and to the one-step kernel
- *   "prop_fused"      1 | 0      PropagationNet as one row-marching kernel | the per-layer kernels (encode + 4 conv + finish)
- *   "tail_streams"    1 .. 8     sub-batches of views in which the regulariser's layers behind conv0 run on concurrent side streams
- *                                (forked from / joined into the caller's stream by events; same kernels, bit-identical results)
- *   "tail_from" / "tail_to"      first / last step of that concurrent section: 1 conv1 + conv2, 3 .. 8 conv3 .. conv8, 9 conv9 + prob,
- *                                10 soft-argmin
- * Unknown names -> V3D_ERR_BAD_ARG; an option this build cannot honour -> V3D_ERR_UNSUPPORTED. */
+ *   "gemm_rounds"     1 | 0      gather-GEMM in rounds for small M | the one-step kernel (bit-identical)
+ *   "gemm_pipe"       1 | 0      sparse convolutions on the loader / matrix pipeline kernel | the rounds kernel (bit-identical)
+ * Unknown names, and gemm_rounds / gemm_pipe values other than 0 and 1 -> V3D_ERR_BAD_ARG. */
 int v3d_set_option(const char* name, int value);
 int v3d_get_option(const char* name, int* value);
 
@@ -365,15 +354,12 @@ int v3d_propagation_pack(const float* const* conv_weight_host, const float* cons
                          const float* const* bn_var_host, int in_dim, int h_dim, float bn_eps,
                          v3d_propagation_weights** out_handle);
 void v3d_propagation_free(v3d_propagation_weights* handle);
-size_t v3d_propagation_workspace_bytes(const v3d_propagation_weights* handle, int B, int H, int W);
-int v3d_propagation_f32(const v3d_propagation_weights* handle, const float* features, const float* depth, int B, int Cf,
-                        int H, int W, float* out, int precision, void* workspace, size_t workspace_bytes, void* stream);
-/* The same network with the nearest-neighbour resize that precedes every call of stage 3 (F.interpolate(depth, size, 'nearest'),
+/* The network, with the nearest-neighbour resize that precedes every call of stage 3 (F.interpolate(depth, size, 'nearest'),
  * mv3d/eval-3dvnet.py:103,111,119) folded into the kernel's addressing (ABI version 5): depth_lo [B, h0, w0] is the depth BEFORE
  * the resize, iy [H] / ix [W] (DEVICE int32) the source row / column of every output row / column -- the caller obtains them
  * from the host framework's own nearest rule; both NULL with h0 == H, w0 == W = no resize.  One row-marching kernel (csrc/propz.hip):
- * the four layers' activations stay in LDS, no workspace.  v3d_propagation_f32 runs the same kernel (developer option
- * "prop_fused" = 0: the per-layer kernels of round 4, other summation orders). */
+ * the four layers' activations stay in LDS, no workspace.  (ABI version 7 removed v3d_propagation_f32 and its workspace: this
+ * call with null tables does the same job.) */
 int v3d_propagation_up_f32(const v3d_propagation_weights* handle, const float* features, const float* depth_lo, int B, int Cf,
                            int H, int W, int h0, int w0, const int32_t* iy, const int32_t* ix, float* out, int precision, void* stream);
 

@@ -17,7 +17,7 @@ NAMES = ['M: wait at B', "M: MFMA phase (B', stores inside)", "H: wait at B'", '
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--refs', type=int, default=64)
-    ap.add_argument('--kernel', default='conv0z', choices=('conv0z', 'conv9z', 'conv12z'))
+    ap.add_argument('--kernel', default='conv0z', choices=('conv0z', 'conv12z'))
     args = ap.parse_args()
     libm = importlib.import_module('3dvnet_amd._lib')
     if os.environ.get('V3D_LIB_OVERRIDE'):

@@ -249,32 +249,6 @@ def test_psv_kernel_variants_bit_identical(cuda):
     assert 'nan' not in ' '.join(outs[0])
 
 
-def test_conv9_prob_depth_march_experiment_agrees_with_tile_kernel(cuda):
-    """csrc/conv9z.hip (developer option c9_kernel = 1, an experiment that only libraries built with -DV3D_EXPERIMENTS carry: the
-    conv9 + skip + prob kernel as a depth march) computes the same products in the same accumulation orders as the default tile
-    kernel: regularised volume and depth bit-identical, on a cfg1 batch and on a volume with partial x tiles and ragged edges.
-    Skipped on the default build (the library refuses the option).  Each variant runs in its own interpreter
-    (scripts/c9_dump.py, which also records which kernel ran)."""
-    import os
-    import subprocess
-    import sys
-    import tempfile
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    with tempfile.TemporaryDirectory() as td:
-        res = []
-        for extra in ([], ['--option=c9_kernel=1']):
-            f = os.path.join(td, 'c9_%d.npz' % len(res))
-            r = subprocess.run([sys.executable, os.path.join(root, 'scripts', 'c9_dump.py'), f] + extra,
-                               capture_output=True, text=True, timeout=600)
-            if r.returncode == 3:
-                pytest.skip('conv9z.hip is not part of the default build (-DV3D_EXPERIMENTS)')
-            assert r.returncode == 0, r.stderr[-2000:]
-            res.append(dict(np.load(f)))
-    for k in ('a', 'b'):
-        assert np.array_equal(res[1]['reg_' + k], res[0]['reg_' + k]) and np.array_equal(res[1]['depth_' + k], res[0]['depth_' + k])
-    assert str(res[0]['kernel']) == 'conv9_prob_kernel' and str(res[1]['kernel']) == 'conv9z_kernel'
-
-
 def test_conv1_conv2_depth_march_agrees_with_tile_kernels(cuda):
     """csrc/conv12z.hip (the default: conv1 + conv2 as one depth march, conv1's output never leaves LDS) against the two tile
     kernels it replaces (developer option c12_march = 0): the same products, conv2's two input-channel chunks summed in another order --

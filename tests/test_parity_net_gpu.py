@@ -178,11 +178,12 @@ def test_process_scene_with_upsampling_matches_oracle_chain(cuda):
         drv.process_scene(scene2, net, 1, cuda, td.CFG, td.OFFSETS, 2, 3, upsample=True)
 
 
-def test_hip_propagation_net_matches_reference_golden_and_oracle_chain(cuda):
-    """SURVEY 8f rank 2 on the HIP path (v3d_propagation_f32: four 3x3 conv layers on split-bf16 matrix cores + the fused
-    softmax / 3x3 propagation kernel): (1) the reference golden N_propagation (33 guide+depth channels); (2) the stage-3
-    chain of eval-3dvnet.py:101-125 -- 1/4, 1/2 and full resolution, 33 / 33 / 4 input channels, image sizes that are not
-    multiples of the 4 x 14 tiles, chunked -- against the oracle chain; (3) chunking does not change bits."""
+def test_hip_propagation_net_matches_golden_and_oracle_chain_fused(cuda):
+    """SURVEY 8f rank 2 on the HIP path (v3d_propagation_up_f32: one row-marching kernel, four 3x3 conv layers on split-bf16
+    matrix cores + the softmax / 3x3 propagation in its epilogue): (1) the reference golden N_propagation (33 guide+depth
+    channels); (2) the stage-3 chain of eval-3dvnet.py:101-125 -- 1/4, 1/2 and full resolution, 33 / 33 / 4 input channels,
+    image sizes that are not multiples of the 40-column strips, chunked -- against the oracle chain; (3) chunking does not
+    change bits."""
     import test_oracle_scene as tos
     syn, up = v3d('synthetic'), v3d('upsampling')
     g = tos.load_golden('N_propagation')
@@ -215,8 +216,7 @@ def test_hip_propagation_net_matches_reference_golden_and_oracle_chain(cuda):
     assert out.shape == (5, 60, 76)
     # round 6 (csrc/propz.hip): a stage is ONE row-marching kernel with the nearest resize in its addressing.  (a) the folded
     # resize equals torch's resize followed by forward(); (b) views are independent: any subset of the batch gives the same
-    # bits; (c) the per-layer kernels of round 4 (developer option prop_fused = 0: other summation orders) agree to 2e-5
-    libm = v3d('_lib')
+    # bits
     with torch.no_grad():
         d0 = depth.to(cuda)
         for n, gd in zip(nets, guides):
@@ -225,12 +225,6 @@ def test_hip_propagation_net_matches_reference_golden_and_oracle_chain(cuda):
             resized = F.interpolate(d0.unsqueeze(1), gd.shape[-2:], mode='nearest')
             assert torch.equal(folded, n(gd, resized))
             assert torch.equal(n.forward_resized(gd[1:4], d0[1:4]), folded[1:4])
-            old = libm.set_option('prop_fused', 0)
-            try:
-                per_layer = n(gd, resized)
-            finally:
-                libm.set_option('prop_fused', old)
-            np.testing.assert_allclose(folded.cpu().numpy(), per_layer.cpu().numpy(), rtol=2e-5, atol=0)
             d0 = folded
         assert torch.equal(d0, out)
         # widths / heights that are not multiples of the 40-column strips, a single row, a single column strip of 3 columns
@@ -692,8 +686,8 @@ def test_sparse_conv_entry_point_equals_the_gather_gemm_call(cuda):
 @pytest.mark.parametrize('M,C,N', [(2816, 128, 128), (13500, 64, 64), (777, 32, 128), (33, 64, 32), (9001, 128, 128),
                                    (40000, 64, 64), (8200, 96, 64)])
 def test_gather_gemm_rounds_kernel_bit_identical_to_one_step_kernel(M, C, N, cuda):
-    """The sparse convolution's two small-M kernels -- the loader / matrix pipeline (gemm_gather_pipe_kernel, the default; 32-,
-    64- and 128-row tiles by M and N) and the rounds of four (offset, K chunk) steps (gemm_gather_rounds_kernel) -- keep the
+    """The sparse convolution's two small-M kernels -- the loader / matrix pipeline (gemm_gather_pipe_kernel, the default; 32-
+    or 64-row tiles by M) and the rounds of four (offset, K chunk) steps (gemm_gather_rounds_kernel) -- keep the
     step order and the MFMA order per accumulator of gemm_gather_kernel: same bits, with absent neighbours, whole absent
     offsets (skipped segments), a ragged last tile, GroupNorm + residual + ReLU in the epilogue."""
     sm = v3d('scenemodeling')

@@ -70,6 +70,8 @@ def build(force=False, verbose=False, strict=False):
             # the fused backbone kernels: every 16-byte LDS read must be the operand of a matrix instruction
             isa_check.check_wide_lds(os.path.join(objdir, 'irb.o'), 'irb_kernel', strict=strict)
             isa_check.check_wide_lds(os.path.join(objdir, 'fpn.o'), 'fpn_level_kernel', strict=strict)
+            # stage 3: the layer-4 softmax epilogue reads its logits 8 / 4 bytes at a time beside the layer-1 matrix wave
+            isa_check.check_wide_lds(os.path.join(objdir, 'propz.o'), 'propz_kernel', strict=strict)
         finally:
             sys.path.pop(0)
     if force or procs or linked != tag or _stale(LIB, objs):

@@ -87,6 +87,28 @@ __device__ __forceinline__ void pz_split4(float a, float b, float c, float d, u3
                pz_pack(c - __uint_as_float(hp.y << 16), d - __uint_as_float(hp.y & 0xffff0000u))};
 }
 
+// 8- and 4-byte LDS reads by hand: two f32x4 reads of the layer-4 logits fed v_max / v_exp beside the layer-1 matrix wave on the
+// same SIMD, the pattern that returned stale upper lanes; plain 4- or 8-byte loads may be merged back into 16-byte
+// reads by the compiler.  The results are valid behind pz_lds_wait; pz_tie orders their consumers behind it.
+template <int OFS>
+__device__ __forceinline__ u32x2 pz_lds_read8(unsigned addr) {
+  u32x2 v;
+  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFS) : "memory");
+  return v;
+}
+template <int OFS>
+__device__ __forceinline__ unsigned pz_lds_read4(unsigned addr) {
+  unsigned v;
+  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFS) : "memory");
+  return v;
+}
+__device__ __forceinline__ void pz_lds_wait() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+template <class T>
+__device__ __forceinline__ void pz_tie(T& v) { asm volatile("" : "+v"(v)); }
+__device__ __forceinline__ unsigned pz_lds_addr(const void* p) {
+  return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
+}
+
 // ---- matrix waves -------------------------------------------------------------------------------------------------------------
 // F32 (V3D_PRECISION_FP32, the reference's arithmetic type): the same kernel on v_mfma_f32_16x16x4_f32 -- a pixel slot holds its
 // channels as fp32 (4 bytes per channel where the split layout has 2 + 2: the same number of 16-byte chunks), the two 16-byte reads of a
@@ -263,9 +285,15 @@ __device__ __forceinline__ void pz_matrix_role(const PropzParams& p, unsigned ch
           const int x = x0 - 4 + c;
           if (c >= 4 && c < 4 + kTWO && x < p.W) {
             float e[9], m = -3.4e38f;
-            const f32x4 q0 = *reinterpret_cast<const f32x4*>(lg + c * 12), q1 = *reinterpret_cast<const f32x4*>(lg + c * 12 + 4);
-            e[0] = q0[0]; e[1] = q0[1]; e[2] = q0[2]; e[3] = q0[3]; e[4] = q1[0]; e[5] = q1[1]; e[6] = q1[2]; e[7] = q1[3];
-            e[8] = lg[c * 12 + 8];
+            // the 9 logits as four 8-byte reads and one 4-byte read (never 16 bytes per lane: DESIGN.md 8.4)
+            const unsigned la = pz_lds_addr(lg + c * 12);
+            u32x2 q0 = pz_lds_read8<0>(la), q1 = pz_lds_read8<8>(la), q2 = pz_lds_read8<16>(la), q3 = pz_lds_read8<24>(la);
+            unsigned q4 = pz_lds_read4<32>(la);
+            pz_lds_wait();
+            pz_tie(q0); pz_tie(q1); pz_tie(q2); pz_tie(q3); pz_tie(q4);
+            e[0] = __uint_as_float(q0.x); e[1] = __uint_as_float(q0.y); e[2] = __uint_as_float(q1.x); e[3] = __uint_as_float(q1.y);
+            e[4] = __uint_as_float(q2.x); e[5] = __uint_as_float(q2.y); e[6] = __uint_as_float(q3.x); e[7] = __uint_as_float(q3.y);
+            e[8] = __uint_as_float(q4);
 #pragma unroll
             for (int k = 0; k < 9; ++k) m = fmaxf(m, e[k]);
             float sum = 0.f;

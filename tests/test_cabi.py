@@ -125,3 +125,23 @@ def test_isa_guard_of_the_fused_decoder():
         assert chk.check(obj + '.missing', strict=False) is None
     finally:
         chk.PINNED, chk.PINNED_COMPILER = pinned, comp
+
+
+@pytest.mark.parametrize('src,kernel', [('irb', 'irb_kernel'), ('fpn', 'fpn_level_kernel'), ('propz', 'propz_kernel')])
+def test_wide_lds_reads_feed_only_matrix_instructions(src, kernel):
+    """The rule of DESIGN.md §8.4 on the default build's objects, independent of the build-time guard (which
+    V3D_SKIP_LDS_CHECK turns off): in the fused backbone kernels and the stage-3 kernel, the first reader of every 16-byte LDS
+    read is a matrix instruction.  The kernels are really in the object and do use 16-byte reads (their matrix operands), so
+    an empty list is not vacuous."""
+    import importlib
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    tag = open(os.path.join(root, '3dvnet_amd', 'build', 'linked_flags')).read().strip()
+    obj = os.path.join(root, '3dvnet_amd', 'build', tag, src + '.o')
+    if not os.path.exists(obj) or not os.path.exists('/opt/rocm/lib/llvm/bin/llvm-objdump'):
+        pytest.skip('no %s.o / llvm tools here' % src)
+    chk = importlib.import_module('3dvnet_amd.isa_check')
+    dis = chk.disassemble(obj)
+    assert re.search(r'^[0-9a-f]+ <[^>]*%s[^>]*>:' % kernel, dis, flags=re.M), '%s not in %s' % (kernel, obj)
+    assert 'ds_read_b128' in dis
+    assert chk.wide_lds_consumers(obj, kernel) == []

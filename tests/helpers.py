@@ -33,6 +33,33 @@ def t(x):
     return torch.from_numpy(np.asarray(x))
 
 
+def state_as(sd, dtype, device=None):
+    """The floating-point entries of a state dict in `dtype` (on `device`): what the functional oracles take as weights."""
+    return {k: v.detach().to(device=device, dtype=dtype) for k, v in sd.items() if v.dtype.is_floating_point}
+
+
+def decoder_reference(xs, pts, pts_feat, pts_batch, sd, chunk=8 * 3136):
+    """oracle.scene.decoder_net(decoder_features(...)) a chunk of query points at a time (the [Nq, 7, 352] feature tensor of
+    a 64-view scene is 4 GB in float64).  The result has the dtype of its inputs."""
+    from oracle import scene as osc
+    out = []
+    for s in range(0, pts.shape[0], chunk):
+        f = osc.decoder_features(xs, pts[s:s + chunk], None if pts_feat is None else pts_feat[s:s + chunk], pts_batch[s:s + chunk])
+        out.append(osc.decoder_net(f, sd))
+    return torch.cat(out)
+
+
+def oracle_levels(xs, dtype):
+    """Level dicts as oracle.scene consumes them, made from the ones a sparse U-Net returned (the oracle's or the HIP
+    module's): the same features and voxel centres, cast to `dtype`, on the CPU."""
+    out = []
+    for x in xs:
+        coords = x['sparse'].coords if 'sparse' in x else x['coords']
+        out.append({'feats': x['feats'].detach().cpu().to(dtype), 'pts': x['pts'].detach().cpu().to(dtype), 'res': float(x['res']),
+                    'batch': x['batch'].detach().cpu().long(), 'stride': int(x['stride']), 'coords': coords.detach().cpu().long()})
+    return out
+
+
 def pinned_project_to_grid(pts_ref, rotmats, tvecs, K, src_idx, img_size):
     """oracle.costvolume.project_to_grid with the host-independent evaluation orders of oracle/pinned.py (P = K [R|t] and
     P [X;1] spelled out with elementwise ops) instead of this host's torch.bmm, whose last bits depend on the host BLAS

@@ -104,6 +104,50 @@ def test_sparse_interpolation_C2a_against_reference_forloop():
     assert [x['feats'].shape[1] for x in xs] == [128, 128, 64]
 
 
+def test_float64_evaluation_of_the_oracles_keeps_its_dtype_and_agrees_with_fp32():
+    """tests/test_full_occupancy_scene_gpu.py takes its references from these oracle functions called with float64 tensors and
+    float64 state dicts.  Here, on the golden scenes: every result IS float64 (nothing inside falls back to fp32) and agrees
+    with the fp32 evaluation within 1e-5 of max|ref| (probabilities: 1e-4 absolute) -- fp32 rounding through 6 / 44 / 4 layers."""
+    from helpers import decoder_reference, oracle_levels, state_as
+    from oracle import backbone as ob
+    syn = v3d('synthetic')
+
+    def agree(a64, a32, what, atol=None):
+        assert a64.dtype == torch.float64 and a32.dtype == torch.float32, (what, a64.dtype, a32.dtype)
+        tol = atol if atol is not None else 1e-5 * float(a64.abs().max())
+        err = float((a64 - a32.double()).abs().max())
+        assert float(a64.abs().max()) > 1e-3 and err <= tol, '%s: float64 vs fp32 oracle %.3g, allowed %.3g' % (what, err, tol)
+
+    g = load_golden('B_pointnet')
+    sd = syn.pointnet_weights(seed=int(g['weights_seed']))
+    x, idx, n = t(g['x_in']), t(g['idx']), int(g['n_idx'])
+    agree(osc.pointnet(x.double(), idx, n, state_as(sd, torch.float64)), osc.pointnet(x, idx, n, sd), 'pointnet')
+
+    g = load_golden('C_forloop')
+    sd_un = syn.sparse_unet_weights(seed=int(g['unet_seed']))
+    sd_dec = syn.decoder_weights(in_dim=320, h_dim=128, seed=int(g['dec_seed']), sharpen=float(g['sharpen']))
+    args = (t(g['anchor_pts']), t(g['anchor_idx3d']), t(g['anchor_batch']), float(g['edge_len']))
+    xs32 = osc.sparse_unet(t(g['x_pointnet']), *args, sd_un)
+    xs64 = osc.sparse_unet(t(g['x_pointnet']).double(), *args, state_as(sd_un, torch.float64))
+    for a, b in zip(xs64, xs32):
+        assert torch.equal(a['coords'], b['coords'])
+        agree(a['feats'], b['feats'], 'sparse U-Net, stride %d' % a['stride'])
+    # the decoder from ONE set of level features (the fp32 ones), as the GPU tests feed it: cast, not recomputed
+    pts, pb = t(g['pts_hyp']), t(g['pts_batch'])
+    p32 = decoder_reference(oracle_levels(xs32, torch.float32), pts, None, pb, sd_dec, chunk=500)
+    p64 = decoder_reference(oracle_levels(xs32, torch.float64), pts.double(), None, pb, state_as(sd_dec, torch.float64), chunk=500)
+    assert torch.equal(p32, osc.decoder_net(osc.decoder_features(xs32, pts, None, pb), sd_dec))      # chunking changes nothing
+    agree(p64, p32, 'decoder probabilities', atol=1e-4)
+    assert float(p64.max()) > 0.5
+
+    sd_e, sd_s = syn.backbone_weights(32, seed=6)
+    img = syn.make_images(2, (64, 96), seed=3)
+    with torch.no_grad():
+        m64 = ob.shrinker(state_as(sd_s, torch.float64), ob.extractor(state_as(sd_e, torch.float64), img.double()))
+    for i, (a, b) in enumerate(zip(m64, ob.backbone_features(sd_e, sd_s, img))):
+        agree(a, b, 'backbone P%d' % (i + 1))
+
+
 def test_misc_H1_H4():
     g = load_golden('H_misc')
     assert np.array_equal(osc.slice_edges(t(g['edges']), 3, 5, 0).numpy(), g['sliced'])

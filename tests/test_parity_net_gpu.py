@@ -409,7 +409,8 @@ def test_fused_decoder_is_deterministic_under_load(cuda):
     table read with 8-byte reads, LDS-DMA weight ring) must stay clean: a 6-view cfg3-shaped scene (18 816 query points = 588
     tiles, more than two per CU), 60 launches while a GEMM runs on a second stream: every launch bit-identical to the first, and
     within 2e-5 of the unfused chain (same products, another summation order: the chain sums k in 32-wide chunks on 16x16x32
-    matrix instructions, the fused kernel in 16-wide steps on 32x32x16 ones, and its softmax sums are shuffle trees)."""
+    matrix instructions, the fused kernel in 16-wide steps on 32x32x16 ones, and its softmax sums are shuffle trees).
+    (Both sides are this library's kernels: test_full_occupancy_scene_gpu.py compares each with a float64 reference at 64 views.)"""
     syn, lm = v3d('synthetic'), v3d('lightningmodel')
     cfg = syn.CONFIGS['cfg3']
     n_ref, k = 6, 2
@@ -689,7 +690,8 @@ def test_gather_gemm_rounds_kernel_bit_identical_to_one_step_kernel(M, C, N, cud
     """The sparse convolution's two small-M kernels -- the loader / matrix pipeline (gemm_gather_pipe_kernel, the default; 32-
     or 64-row tiles by M) and the rounds of four (offset, K chunk) steps (gemm_gather_rounds_kernel) -- keep the
     step order and the MFMA order per accumulator of gemm_gather_kernel: same bits, with absent neighbours, whole absent
-    offsets (skipped segments), a ragged last tile, GroupNorm + residual + ReLU in the epilogue."""
+    offsets (skipped segments), a ragged last tile, GroupNorm + residual + ReLU in the epilogue.
+    (Kernel against kernel: test_full_occupancy_scene_gpu.py compares the default one with a float64 reference on real coordinate maps.)"""
     sm = v3d('scenemodeling')
     g = torch.Generator().manual_seed(M)
     w = torch.randn(27, C, N, generator=g) * 0.05

@@ -72,6 +72,8 @@ def build(force=False, verbose=False, strict=False):
             isa_check.check_wide_lds(os.path.join(objdir, 'fpn.o'), 'fpn_level_kernel', strict=strict)
             # stage 3: the layer-4 softmax epilogue reads its logits 8 / 4 bytes at a time beside the layer-1 matrix wave
             isa_check.check_wide_lds(os.path.join(objdir, 'propz.o'), 'propz_kernel', strict=strict)
+            # depth fusion: the per-pixel chain of fuse_depths_kernel stays in registers
+            isa_check.check_no_scratch(os.path.join(objdir, 'fusion.o'), 'fuse_depths_kernel', strict=strict)
         finally:
             sys.path.pop(0)
     if force or procs or linked != tag or _stale(LIB, objs):

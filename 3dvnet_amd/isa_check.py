@@ -60,13 +60,15 @@ def disassemble(obj):
         raise GuardUnavailable('cannot disassemble %s: %s' % (obj, e))
 
 
-def signature(obj):
-    """-> ({ds_read mnemonic: count}, number of scratch instructions) of the fused kernel in `obj`."""
+def signature(obj, kernel=None):
+    """-> ({ds_read mnemonic: count}, number of scratch instructions) of the kernels in `obj` whose symbol matches the regular
+    expression `kernel` (default: the fused decoder)."""
+    kernel = KERNEL if kernel is None else kernel
     inside, counts, scratch, seen = False, collections.Counter(), 0, False
     for line in disassemble(obj).splitlines():
         m = re.match(r'^[0-9a-f]+ <(.*)>:', line)
         if m:
-            inside = KERNEL in m.group(1)
+            inside = re.search(kernel, m.group(1)) is not None
             seen = seen or inside
             continue
         if inside:
@@ -76,7 +78,7 @@ def signature(obj):
             if re.search(r'\bscratch_(load|store)', line):
                 scratch += 1
     if not seen:
-        raise GuardUnavailable('%s not found in %s' % (KERNEL, obj))
+        raise GuardUnavailable('%s not found in %s' % (kernel, obj))
     return dict(sorted(counts.items())), scratch
 
 
@@ -166,6 +168,27 @@ def check_wide_lds(obj, kernel_pattern, strict=False):
     if bad:
         raise RuntimeError('a 16-byte LDS read feeds a non-matrix instruction (DESIGN.md §8.4) in %s:\n  %s\n  -> %s\n(%d such reads)'
                            % (bad[0][0], bad[0][1], bad[0][2], len(bad)))
+    return 0
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# The depth-fusion kernel (csrc/fusion.hip): a thread keeps its pixel's whole chain in registers.  The rule is the first one above,
+# for another kernel: not a single scratch_load / scratch_store instruction in its code.
+def scratch_count(obj, kernel_pattern):
+    """-> number of scratch_load / scratch_store instructions in the kernels of `obj` whose symbol matches `kernel_pattern`."""
+    return signature(obj, kernel_pattern)[1]
+
+
+def check_no_scratch(obj, kernel_pattern, strict=False):
+    try:
+        scratch = scratch_count(obj, kernel_pattern)
+    except GuardUnavailable as e:
+        if strict:
+            raise RuntimeError('ISA guard (%s) could not run: %s' % (kernel_pattern, e))
+        sys.stderr.write('isa_check: guard NOT run (%s)\n' % e)
+        return None
+    if scratch:
+        raise RuntimeError('%s contains %d scratch instructions: the kernel must not spill' % (kernel_pattern, scratch))
     return 0
 
 

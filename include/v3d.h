@@ -452,6 +452,39 @@ void v3d_fpn_free(v3d_fpn_weights* handle);
 int v3d_fpn_level_f32(const v3d_fpn_weights* handle, const float* x, const float* coarse_inner, int n, int H, int W,
                       float* inner_out, float* out, void* stream);
 
+/* Multi-view depth fusion (csrc/fusion.hip; ABI version 8): the depth maps of a scene -> a fused point cloud with the semantics of
+ * mv3d/eval/pointcloudfusion_custom.py (process_depth :10-95, process_scene :98-116), the step mv3d/eval/processresults.py:276
+ * runs on the preds.npz record.  Pixel (x, y) of reference view r with depth d is lifted to X = P_r^-1 (K_r^-1 [x d, y d, d]);
+ * for each source s in list order q = K_s (R_s X + t_s), (u, v) = q_xy / q_z; the source is valid when q_z > 1e-4, 0 <= u <= w-1,
+ * 0 <= v <= h-1 and |q_z - z_s| < z_thresh, z_s = the nearest texel of d_s (grid_sample nearest / align_corners / zero padding);
+ * a valid source adds X_s = R_s^T (K_s^-1 [u z_s, v z_s, z_s] - t_s).  pts = (X + sum X_s) / (n_valid + 1), fp32, list order.
+ *   v3d_fusion_workspace_bytes  scratch of both calls for n_img maps of h x w (0 for sizes the calls reject); calls issued on one
+ *                         stream may share one workspace
+ *   v3d_fuse_depths_f32   depths [n_img, h, w]; cams [n_img, 48] camera blocks: [0..8] K, [9..17] K^-1, [18..26] R, [27..29] t,
+ *                         [30..41] rows 0..2 of P^-1 (3 x 4, row major), [42..47] unused -- the inverses come from the caller
+ *                         (torch.inverse) so that their last bits are the reference's.  ref_img_host [n_ref] (HOST) = image index
+ *                         of every reference, NULL = all n_img images (n_ref == n_img).  edge_ofs_host [n_ref + 1] / edge_src_host
+ *                         (HOST, CSR as in v3d_psv_variance_*): the source list of every reference, at most n_img^2 entries; both
+ *                         NULL = all other images in ascending order.  The lists are checked here and copied to the workspace on
+ *                         `stream` with hipMemcpyAsync: from ordinary (pageable) host memory the runtime has taken its copy when the
+ *                         call returns and the arrays may be released; arrays in PINNED host memory must stay unchanged until the
+ *                         stream has passed the call.  -> pts [n_ref, h w, 3], n_valid [n_ref, h w] int32, dense, every element written.
+ *                         Errors: V3D_ERR_BAD_SHAPE for h or w < 2 (the normalisation divides by w - 1) and bad counts,
+ *                         V3D_ERR_BAD_ARG for a reference / source index outside [0, n_img) or a malformed list.
+ *   v3d_fusion_compact    keep = n_valid >= n_consistent_thresh -> all_valid [n_ref, h, w] bytes, view_count [n_ref], view_ofs
+ *                         [n_ref + 1] (exclusive scan), the kept points out_pts [*, 3] and colours out_rgb [*, px_bytes] in (view,
+ *                         row-major pixel) order, their number in the device word `total`.  images [n_ref, h w, px_bytes] = the
+ *                         references' colours, px_bytes bytes per pixel of any type (NULL with out_rgb NULL: points only);
+ *                         out_pts / out_rgb hold n_ref h w entries (the worst case).  Stable and atomic-free: bit-identical
+ *                         across launches. */
+size_t v3d_fusion_workspace_bytes(int n_img, int h, int w);
+int v3d_fuse_depths_f32(const float* depths, const float* cams, int n_img, int h, int w, const int32_t* ref_img_host, int n_ref,
+                        const int32_t* edge_ofs_host, const int32_t* edge_src_host, double z_thresh, float* pts, int32_t* n_valid,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int v3d_fusion_compact(const int32_t* n_valid, const float* pts, const void* images, int px_bytes, int n_ref, int h, int w,
+                       int n_consistent_thresh, uint8_t* all_valid, int32_t* view_count, int32_t* view_ofs, float* out_pts,
+                       void* out_rgb, int32_t* total, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

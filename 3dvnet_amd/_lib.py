@@ -13,7 +13,7 @@ import torch  # noqa: F401  -- must be imported BEFORE the dlopen below: the lib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib3dvnet_hip.so')
-ABI_VERSION = 8
+ABI_VERSION = 9
 PRECISION = {'split_bf16': 0, 'fp32': 1}      # V3D_PRECISION_* of include/v3d.h
 
 
@@ -131,6 +131,14 @@ SIGNATURES = {
     'v3d_fuse_depths_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_int),
                                     ctypes.POINTER(c_int), c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'v3d_fusion_compact': (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 7 + [c_size_t, c_void_p]),
+    'v3d_cloud_downsample_workspace_bytes': (c_size_t, [c_int]),
+    'v3d_cloud_downsample_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_double, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_size_t, c_void_p]),
+    'v3d_cloud_status': (c_int, [c_void_p, c_size_t, ctypes.POINTER(c_int), c_void_p]),
+    'v3d_nn_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'v3d_nn_query_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'v3d_cloud_metrics_workspace_bytes': (c_size_t, []),
+    'v3d_cloud_metrics_f64': (c_int, [c_void_p, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 

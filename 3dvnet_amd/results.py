@@ -58,3 +58,21 @@ def depth_metrics_2d(depth_pred, depth_gt, pred_valid=None):
                    d_125_2=per_image((ratio < 1.25 ** 2).float()).mean(),
                    d_125_3=per_image((ratio < 1.25 ** 3).float()).mean())
     return out
+
+
+def average_metrics(all_metrics):
+    """Average of per-scene metric dicts after the reference's ``calc_avg_metrics`` (processresults.py:415-422): the plain
+    mean over scenes for the five 3D keys (acc, comp, prec, recal, fscore), the mean weighted by the scenes' view counts
+    ``'n'`` for every other key (those need ``'n'`` in every dict).  The keys are those of the first dict."""
+    all_metrics = list(all_metrics)
+    first = all_metrics[0]
+    n_sum = np.sum([m['n'] for m in all_metrics]) if 'n' in first else 1.
+    avg = {}
+    for k in first:
+        if k == 'n':
+            continue
+        if k in ('acc', 'comp', 'prec', 'recal', 'fscore'):
+            avg[k] = float(np.mean([m[k] for m in all_metrics]))
+        else:
+            avg[k] = float(np.sum([m['n'] * m[k] for m in all_metrics])) / float(n_sum)
+    return avg

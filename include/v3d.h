@@ -485,6 +485,47 @@ int v3d_fusion_compact(const int32_t* n_valid, const float* pts, const void* ima
                        int n_consistent_thresh, uint8_t* all_valid, int32_t* view_count, int32_t* view_ofs, float* out_pts,
                        void* out_rgb, int32_t* total, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Scoring of a fused point cloud (csrc/cloudmetrics.hip; ABI version 9): the three steps mv3d/eval/processresults.py:283-295 runs
+ * on the fused cloud -- voxel down-sample, nearest neighbours in both directions (mv3d/eval/metricfunctions.py:102-124), the five
+ * numbers of eval_mesh (:70-99).
+ *   v3d_cloud_downsample_f32  Open3D's VoxelDownSample as documented (restated; not pinned against the package).  pts [n, 3] fp32;
+ *                         the rows in use are the first min(max(*n_dev, 0), n) when n_dev (a DEVICE int32 word, e.g. the `total` of
+ *                         v3d_fusion_compact) is given, else all n.  vmin = double(min over rows) - voxel_size / 2, cell =
+ *                         floor((double(p) - vmin) / voxel_size) per axis, key = x 2^42 + y 2^21 + z.  Output row of a cell = the
+ *                         double-precision mean of its member rows, summed in original row order, rounded once to fp32; attr
+ *                         [n, n_attr] (NULL with n_attr 0) is averaged the same way.  Output order: ascending key.  out_pts
+ *                         [n, 3] / out_attr [n, n_attr] hold n rows (the worst case); the number of cells lands in the DEVICE word
+ *                         out_count.  Data-dependent errors never fail the call: they set out_count to the NEGATED error bits
+ *                         (1 non-finite coordinate, 2 extent / voxel_size >= 2^21 on an axis, 4 voxel_size not positive and
+ *                         finite) and are reported by v3d_cloud_status.  No atomics: bit-identical across launches.
+ *   v3d_cloud_status      reads the status of the last down-sample call on this workspace (synchronises the stream): returns
+ *                         V3D_OK and the number of output rows in *n_out_host (HOST, may be NULL), or V3D_ERR_BAD_ARG (bits 1, 4) /
+ *                         V3D_ERR_BAD_SHAPE (bit 2) with *n_out_host = 0.
+ *   v3d_nn_query_f32      for every query row the nearest target row: idx [n_query] = its index in the target's own row order,
+ *                         dist [n_query] = sqrt(dx^2 + dy^2 + dz^2) evaluated in fp32 from fp32 differences.  Exact (no radius, no
+ *                         approximation) and deterministic: the result is the minimum of (fp32 distance, target row).  The search
+ *                         index (Morton-sorted copy of the target, cell table) is built in the workspace by every call.
+ *                         n_query == 0: nothing is done; n_target == 0: idx = -1, dist = +inf.  Coordinates must be finite (a NaN
+ *                         row is never a neighbour and finds none).
+ *   v3d_cloud_metrics_f64 dist_pred [n_pred] = distance of every predicted row to the target cloud, dist_target [n_target] = of
+ *                         every target row to the predicted cloud -> out [5] doubles (DEVICE): acc = mean(dist_pred), comp =
+ *                         mean(dist_target), prec / recal = share of double(d) < threshold in dist_pred / dist_target, fscore =
+ *                         2 prec recal / (prec + recal + 1e-8).  Double sums in a fixed two-stage order.  An empty array gives
+ *                         NaN, as the reference's NumPy means do.
+ * Host-side errors (returned before anything is enqueued): null pointers, negative counts, a too-small workspace,
+ * threshold <= 0. */
+size_t v3d_cloud_downsample_workspace_bytes(int n);
+int v3d_cloud_downsample_f32(const float* pts, const float* attr, int n_attr, int n, const int32_t* n_dev, double voxel_size,
+                             float* out_pts, float* out_attr, int32_t* out_count, void* workspace, size_t workspace_bytes,
+                             void* stream);
+int v3d_cloud_status(const void* workspace, size_t workspace_bytes, int32_t* n_out_host, void* stream);
+size_t v3d_nn_workspace_bytes(int n_target, int n_query);
+int v3d_nn_query_f32(const float* target, int n_target, const float* query, int n_query, int32_t* idx, float* dist,
+                     void* workspace, size_t workspace_bytes, void* stream);
+size_t v3d_cloud_metrics_workspace_bytes(void);
+int v3d_cloud_metrics_f64(const float* dist_pred, int n_pred, const float* dist_target, int n_target, double threshold,
+                          double* out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

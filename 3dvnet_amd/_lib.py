@@ -139,6 +139,10 @@ SIGNATURES = {
     'v3d_nn_query_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'v3d_cloud_metrics_workspace_bytes': (c_size_t, []),
     'v3d_cloud_metrics_f64': (c_int, [c_void_p, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # additive within ABI version 9 (include/v3d.h)
+    'v3d_tsdf_integrate_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_float_p, c_double, c_void_p,
+                                       c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'v3d_tsdf_normalize_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -74,6 +74,8 @@ def build(force=False, verbose=False, strict=False):
             isa_check.check_wide_lds(os.path.join(objdir, 'propz.o'), 'propz_kernel', strict=strict)
             # depth fusion: the per-pixel chain of fuse_depths_kernel stays in registers
             isa_check.check_no_scratch(os.path.join(objdir, 'fusion.o'), 'fuse_depths_kernel', strict=strict)
+            # TSDF integration: the five running values of a voxel stay in registers across the view loop
+            isa_check.check_no_scratch(os.path.join(objdir, 'tsdf.o'), 'tsdf_integrate_kernel', strict=strict)
             # nearest neighbour: the per-query search state of nn_query_kernel stays in registers
             isa_check.check_no_scratch(os.path.join(objdir, 'cloudmetrics.o'), 'nn_query_kernel', strict=strict)
         finally:

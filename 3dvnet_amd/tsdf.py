@@ -1,0 +1,256 @@
+"""TSDF integration on the device: the depth maps ``results.write_preds`` leaves behind -> a truncated signed distance
+volume with weights and colours (``mv3d/eval/tsdf_atlas.py``: ``TSDFFusion`` :341-463, ``TSDF`` :70-159, driven by the
+``run_tsdf`` branch of ``mv3d/eval/processresults.py:297-383``).  The arithmetic is ``csrc/tsdf.hip`` behind
+``v3d_tsdf_integrate_f32`` / ``v3d_tsdf_normalize_f32``; this module is the plumbing around it:
+
+  * ``TSDFFusion``           the reference's constructor, ``reset`` / ``integrate`` / ``get_tsdf``, plus ``integrate_batch``
+                             (N views in one launch; the same bits as N ``integrate`` calls);
+  * ``TSDF``                 the holder with ``to`` / ``save`` / ``load`` and the reference's npz keys;
+  * ``projection_matrices``  K [R | t] (processresults.py:19-24);
+  * ``volume_bounds``        the scene's volume from the quantiles of the back-projected depths (:324-357);
+  * ``fuse_preds_tsdf``      from a ``preds.npz`` record (path or mapping) to the ``TSDF``.
+
+There is no CPU fallback: without the library or a HIP device every integrating entry raises ``V3DLibraryError``.
+Meshes (marching cubes), ``TSDF.transform`` and the label volume are not provided.
+"""
+import ctypes
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+from . import fusion as _fusion
+
+
+def projection_matrices(K, poses):
+    """[N, 3, 3] intrinsics, [N, 4, 4] world->camera poses -> [N, 3, 4] projections K [R | t]: the batched product of K with
+    a zero fourth column and the pose, as the reference forms it, on the tensors' device."""
+    K, poses = torch.as_tensor(K), torch.as_tensor(poses)
+    if K.dim() != 3 or K.shape[1:] != (3, 3) or poses.shape != (K.shape[0], 4, 4):
+        raise ValueError('projection_matrices: K [N, 3, 3] and poses [N, 4, 4] expected, got %s and %s'
+                         % (tuple(K.shape), tuple(poses.shape)))
+    K4 = torch.cat((K, torch.zeros((K.shape[0], 3, 1), dtype=K.dtype, device=K.device)), dim=2)
+    return torch.bmm(K4, poses.to(K))
+
+
+def _backproject(depths, P):
+    """[n, h, w] depths, [n, 3, 4] projections -> [n, h w, 3] world points: P4^-1 [x, y, 1, 1 / d] de-homogenised.  A zero
+    depth gives NaN rows."""
+    n, h, w = depths.shape
+    ys, xs = torch.meshgrid(torch.arange(h).type_as(depths), torch.arange(w).type_as(depths), indexing='ij')
+    pix = torch.stack((xs, ys, torch.ones_like(xs)), dim=0)[None].repeat(n, 1, 1, 1)
+    pix = torch.cat((pix, 1. / depths.unsqueeze(1)), dim=1)
+    last = torch.tensor([[0, 0, 0, 1]]).type_as(P)[None].repeat(n, 1, 1)
+    P_inv = torch.cat((P, last), dim=1).inverse()
+    X = torch.bmm(P_inv, pix.view(n, 4, h * w))
+    return (X[:, :3] / X[:, 3:]).transpose(2, 1)
+
+
+def volume_bounds(depths, K, poses, vol_prcnt=.995, vol_margin=1.5, vox_res=.04, img_batch=100):
+    """The reference's bounds rule (processresults.py:324-357).  Per batch of ``img_batch`` views the depths are
+    back-projected, rows with a NaN dropped, and the per-axis quantiles at ``1 - vol_prcnt`` / ``vol_prcnt`` (NumPy's linear
+    rule on the fp32 values, on the host, as the reference takes them) widened by ``vol_margin``; an empty batch is skipped;
+    across batches the lower bound is a running minimum and the upper a running maximum.  ``depths`` [N, h, w] may live on
+    the host or a device (the back-projection runs where they live); K and poses are host tensors / arrays.
+    -> ``(origin [3] fp32, vol_max [3] fp32, vol_dim list of 3 ints)``, ``vol_dim = int((vol_max - origin) / vox_res)``.
+    Once per scene, not a hot path: stock torch ops and one host quantile per batch."""
+    depths = torch.as_tensor(depths)
+    K, poses = torch.as_tensor(K).float().cpu(), torch.as_tensor(poses).float().cpu()
+    n = depths.shape[0]
+    origin = vol_max = None
+    for start in range(0, n, int(img_batch)):
+        d = depths[start:start + img_batch].float()
+        P = projection_matrices(K[start:start + img_batch], poses[start:start + img_batch]).to(d.device)
+        pts = _backproject(d, P).reshape(-1, 3)
+        pts = pts[~torch.any(torch.isnan(pts), dim=1)].cpu().numpy()
+        if pts.shape[0] == 0:
+            continue
+        lo = torch.as_tensor(np.quantile(pts, 1 - vol_prcnt, axis=0) - vol_margin).float()
+        hi = torch.as_tensor(np.quantile(pts, vol_prcnt, axis=0) + vol_margin).float()
+        origin = lo if origin is None else torch.minimum(origin, lo)
+        vol_max = hi if vol_max is None else torch.maximum(vol_max, hi)
+    if origin is None:
+        raise ValueError('volume_bounds: no depth map has a usable pixel')
+    vol_dim = ((vol_max - origin) / vox_res).int().tolist()
+    return origin, vol_max, vol_dim
+
+
+class TSDF:
+    """Holder of a TSDF volume with its metadata (tsdf_atlas.py:70-159): ``voxel_size``, ``origin`` [1, 3], ``tsdf_vol``
+    [nx, ny, nz], ``attribute_vols`` (``'weight'`` [nx, ny, nz], ``'color'`` [3, nx, ny, nz]) and ``attributes``.
+
+    ``save`` writes the reference's npz keys: ``origin``, ``voxel_size``, ``tsdf`` and one key per attribute volume /
+    attribute.  ``load`` reads them back the way the reference does, including its placement of ``weight`` (and
+    ``tsdf_point_cloud``) under ``attributes`` rather than ``attribute_vols``.  The reference's ``tsdf_point_cloud`` attribute
+    (a coloured marching-cubes vertex list ``get_tsdf`` attaches) needs marching cubes and is never produced here;
+    ``get_mesh`` and ``transform`` are not provided."""
+
+    def __init__(self, voxel_size, origin, tsdf_vol, attribute_vols=None, attributes=None):
+        self.voxel_size = voxel_size
+        self.origin = origin
+        self.tsdf_vol = tsdf_vol
+        self.attribute_vols = attribute_vols if attribute_vols is not None else {}
+        self.attributes = attributes if attributes is not None else {}
+        self.device = tsdf_vol.device
+
+    def save(self, fname):
+        data = {'origin': self.origin.cpu().numpy(), 'voxel_size': self.voxel_size,
+                'tsdf': self.tsdf_vol.detach().cpu().numpy()}
+        for key, value in self.attribute_vols.items():
+            data[key] = value.detach().cpu().numpy()
+        for key, value in self.attributes.items():
+            data[key] = value.cpu().numpy()
+        np.savez_compressed(fname, **data)
+
+    @classmethod
+    def load(cls, fname, voxel_types=None):
+        """``voxel_types``: which volumes to load besides the tsdf (e.g. ``['color']``); None = all."""
+        with np.load(fname) as data:
+            voxel_size = data['voxel_size'].item()
+            origin = torch.as_tensor(data['origin']).view(1, 3)
+            tsdf_vol = torch.as_tensor(data['tsdf'])
+            attribute_vols, attributes = {}, {}
+            for key in ('weight', 'tsdf_point_cloud'):
+                if key in data:
+                    attributes[key] = torch.as_tensor(data[key])
+            if 'color' in data and (voxel_types is None or 'color' in voxel_types):
+                attribute_vols['color'] = torch.as_tensor(data['color'])
+            if 'instance' in data and (voxel_types is None or 'instance' in voxel_types or 'semseg' in voxel_types):
+                attribute_vols['instance'] = torch.as_tensor(data['instance'])
+        return cls(voxel_size, origin, tsdf_vol, attribute_vols, attributes)
+
+    def to(self, device):
+        self.origin = self.origin.to(device)
+        self.tsdf_vol = self.tsdf_vol.to(device)
+        self.attribute_vols = {key: value.to(device) for key, value in self.attribute_vols.items()}
+        self.attributes = {key: value.to(device) for key, value in self.attributes.items()}
+        self.device = device
+        return self
+
+
+class TSDFFusion:
+    """Accumulates depth maps into a TSDF volume (tsdf_atlas.py:341-463) with the reference's constructor order.
+    ``tsdf_vol`` holds the running SUM of truncated distances (fresh: -1, as the reference's constructor fills it and
+    never-seen voxels keep it; after ``reset()``: +1, as the reference's ``reset`` fills it), ``weight_vol`` the number of
+    views that saw a voxel, ``color_vol`` [3, n] the summed colours (None with ``color=False``).  ``device=None`` takes the
+    first HIP device (the host when there is none: such an object can be built and reset, not integrated into)."""
+
+    def __init__(self, voxel_dim=(128, 128, 128), voxel_size=.02, origin=(0, 0, 0), trunc_ratio=3, device=None,
+                 color=True, label=False):
+        if label:
+            raise NotImplementedError('TSDFFusion: the label volume is not provided (the evaluation path passes label=False)')
+        if device is None:
+            device = torch.device('cuda:0' if torch.cuda.is_available() else 'cpu')
+        device = torch.device(device)
+        nx, ny, nz = (int(v) for v in voxel_dim)
+        if min(nx, ny, nz) < 1 or nx * ny * nz >= 2 ** 31:
+            raise ValueError('TSDFFusion: voxel_dim %r (positive, fewer than 2^31 voxels)' % (voxel_dim,))
+        self.voxel_dim = voxel_dim
+        self.voxel_size = voxel_size
+        self.origin = torch.as_tensor(origin).detach().clone().to(dtype=torch.float, device=device).view(1, 3)
+        self.trunc_margin = voxel_size * trunc_ratio
+        self.device = device
+        self._dims = (nx, ny, nz)
+        self._origin_host = (ctypes.c_float * 3)(*[float(v) for v in self.origin.view(3).cpu()])
+        self.tsdf_vol = -torch.ones(nx * ny * nz, device=device)
+        self.weight_vol = torch.zeros(nx * ny * nz, device=device)
+        self.color_vol = torch.zeros((3, nx * ny * nz), device=device) if color else None
+        self.label_vol = None
+
+    def reset(self):
+        self.tsdf_vol.fill_(1)
+        self.weight_vol.fill_(0)
+        if self.color_vol is not None:
+            self.color_vol.fill_(0)
+
+    def _lib(self, what):
+        lib = _lib.load()
+        if not torch.cuda.is_available() or not self.tsdf_vol.is_cuda:
+            raise _lib.V3DLibraryError('%s: the volume must live on a HIP device (no CPU fallback)' % what)
+        return lib
+
+    def integrate_batch(self, projections, depths, colors=None):
+        """N views in ONE launch, applied in the given order: projections [N, 3, 4], depths [N, h, w], colors [N, 3, h, w]
+        (required exactly when the volume carries colour).  Gives the bits of N ``integrate`` calls."""
+        lib = self._lib('TSDFFusion.integrate_batch')
+        projections, depths = torch.as_tensor(projections), torch.as_tensor(depths)
+        if depths.dim() != 3 or projections.dim() != 3 or projections.shape != (depths.shape[0], 3, 4):
+            raise ValueError('integrate_batch: projections [N, 3, 4] and depths [N, h, w] expected, got %s and %s'
+                             % (tuple(projections.shape), tuple(depths.shape)))
+        n, h, w = depths.shape
+        if (colors is None) != (self.color_vol is None):
+            raise ValueError('integrate_batch: colours are required exactly when the volume was built with color=True')
+        P = projections.to(self.device, torch.float32).contiguous()
+        d = depths.to(self.device, torch.float32).contiguous()
+        img = None
+        if colors is not None:
+            if tuple(colors.shape) != (n, 3, h, w):
+                raise ValueError('integrate_batch: colors must be [N, 3, h, w] = %s, got %s' % ((n, 3, h, w), tuple(colors.shape)))
+            img = torch.as_tensor(colors).to(self.device, torch.float32).contiguous()
+        nx, ny, nz = self._dims
+        with torch.cuda.device(self.device):
+            _lib.check(lib.v3d_tsdf_integrate_f32(_lib.ptr(self.tsdf_vol), _lib.ptr(self.weight_vol), _lib.ptr(self.color_vol),
+                                                  nx, ny, nz, float(self.voxel_size), self._origin_host,
+                                                  float(self.trunc_margin), _lib.ptr(P), _lib.ptr(d), _lib.ptr(img), n, h, w,
+                                                  _lib.stream_ptr(self.device)), 'v3d_tsdf_integrate_f32')
+
+    def integrate(self, projection, depth, color=None, label=None):
+        """One view (tsdf_atlas.py:390): projection [3, 4], depth [h, w], color [3, h, w]."""
+        if label is not None:
+            raise NotImplementedError('TSDFFusion.integrate: the label volume is not provided')
+        self._lib('TSDFFusion.integrate')
+        self.integrate_batch(torch.as_tensor(projection)[None], torch.as_tensor(depth)[None],
+                             None if color is None else torch.as_tensor(color)[None])
+
+    def get_tsdf(self):
+        """-> ``TSDF`` with the averaged distances [nx, ny, nz] (sum / weight where weight > 0, the fill value elsewhere),
+        ``attribute_vols['weight']`` and, with colour, ``['color']`` [3, nx, ny, nz] averaged the same way.  The reference's
+        ``tsdf_point_cloud`` attribute is left out (marching cubes)."""
+        lib = self._lib('TSDFFusion.get_tsdf')
+        nx, ny, nz = self._dims
+        tsdf_vol = torch.empty_like(self.tsdf_vol)
+        color_vol = None if self.color_vol is None else torch.empty_like(self.color_vol)
+        with torch.cuda.device(self.device):
+            _lib.check(lib.v3d_tsdf_normalize_f32(_lib.ptr(self.tsdf_vol), _lib.ptr(self.weight_vol), _lib.ptr(self.color_vol),
+                                                  nx * ny * nz, _lib.ptr(tsdf_vol), _lib.ptr(color_vol),
+                                                  _lib.stream_ptr(self.device)), 'v3d_tsdf_normalize_f32')
+        attribute_vols = {'weight': self.weight_vol.view(nx, ny, nz)}
+        if color_vol is not None:
+            attribute_vols['color'] = color_vol.view(3, nx, ny, nz)
+        return TSDF(self.voxel_size, self.origin, tsdf_vol.view(nx, ny, nz), attribute_vols)
+
+
+def prepare_preds_tsdf(preds, images):
+    """Host preparation of a ``preds.npz`` record (path or mapping) and the scene's images [N, H, W, 3] (RGB, any dtype) for
+    the TSDF branch (processresults.py:306-320): poses from ``rotmats`` / ``tvecs``, images flipped to BGR, made float
+    [N, 3, H, W] and bilinearly resized to the depth maps' size.  No probability masking: the reference's TSDF branch does
+    none.  -> ``(depths [N, h, w], poses [N, 4, 4], K [N, 3, 3], images [N, 3, h, w])`` fp32 host tensors."""
+    if isinstance(preds, (str, bytes)) or hasattr(preds, '__fspath__'):
+        with np.load(preds) as f:
+            preds = {k: f[k] for k in f.files}
+    rec = {k: v for k, v in preds.items() if k not in ('init_prob', 'final_prob')}
+    depths, poses, K = _fusion.prepare_preds(rec)
+    images = torch.as_tensor(np.asarray(images))
+    if images.dim() != 4 or images.shape[0] != depths.shape[0] or images.shape[-1] != 3:
+        raise ValueError('prepare_preds_tsdf: images must be [N, H, W, 3] with N = %d, got %s'
+                         % (depths.shape[0], tuple(images.shape)))
+    images = images[..., [2, 1, 0]].permute(0, 3, 1, 2).float()
+    images = F.interpolate(images, tuple(depths.shape[-2:]), mode='bilinear')
+    return torch.from_numpy(depths), torch.from_numpy(poses), torch.from_numpy(K), images
+
+
+def fuse_preds_tsdf(preds, images, vox_res=.04, trunc_ratio=3, vol_prcnt=.995, vol_margin=1.5, img_batch=100, color=True,
+                    device=None, return_fusion=False):
+    """The ``run_tsdf`` branch up to ``get_tsdf()``: bounds from ``volume_bounds``, one ``integrate_batch`` per chunk of
+    ``img_batch`` views, ``get_tsdf()``.  -> ``TSDF`` (on the device); ``return_fusion=True`` -> ``(TSDF, TSDFFusion)``."""
+    _lib.load()
+    dev = _fusion._device(device)
+    depths, poses, K, images = prepare_preds_tsdf(preds, images)
+    origin, _, vol_dim = volume_bounds(depths.to(dev), K, poses, vol_prcnt, vol_margin, vox_res, img_batch)
+    fus = TSDFFusion(vol_dim, vox_res, origin, trunc_ratio, dev, color=color, label=False)
+    for start in range(0, depths.shape[0], int(img_batch)):
+        sl = slice(start, start + int(img_batch))
+        fus.integrate_batch(projection_matrices(K[sl], poses[sl]), depths[sl], images[sl] if color else None)
+    tsdf = fus.get_tsdf()
+    return (tsdf, fus) if return_fusion else tsdf

@@ -526,6 +526,33 @@ size_t v3d_cloud_metrics_workspace_bytes(void);
 int v3d_cloud_metrics_f64(const float* dist_pred, int n_pred, const float* dist_target, int n_target, double threshold,
                           double* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* TSDF integration of depth maps (csrc/tsdf.hip): the semantics of mv3d/eval/tsdf_atlas.py TSDFFusion.integrate (:390-443) and
+ * get_tsdf (:453-463), the volume mv3d/eval/processresults.py:359-382 builds from the preds.npz record.  ABI version: STILL 9.
+ * These two entry points are purely additive -- new symbols, no changed signature -- so a caller built against version 9 keeps
+ * working and v3d_version() is not bumped.
+ *   v3d_tsdf_integrate_f32  applies n views, in the given order, to a volume of nx x ny x nz voxels, IN PLACE (a fresh volume, one
+ *                         view at a time, or a scene in chunks).  State, flat index (x ny + y) nz + z: tsdf [nx ny nz] = the running
+ *                         sum (fresh: -1, after the reference's reset(): +1), weight [nx ny nz] (fresh: 0), color [3, nx ny nz]
+ *                         (fresh: 0; NULL together with images: no colour).  voxel_size, trunc_margin and origin [3] (HOST, read
+ *                         before the call returns) are taken as fp32.  projections [n, 12] (DEVICE) = the 3 x 4 matrices K [R | t],
+ *                         row major; depths [n, h, w]; images [n, 3, h, w] fp32.  Per voxel and view, all fp32: world = fl(fl(i *
+ *                         voxel_size) + origin) per axis; c_r = row r of P . [world; 1] as a k-ordered FMA chain; (px, py) =
+ *                         round-half-even(c0 / c2, c1 / c2); valid = px >= 0, py >= 0, px < w, py < h, c2 > 0 (decided on the
+ *                         floats: a NaN or huge coordinate is invalid), d = depths[py, px] > 0, dist = min((d - c2) / trunc_margin,
+ *                         1) > -1; a valid view sets tsdf = dist when weight == 0, else tsdf += dist; weight += 1; color[c] +=
+ *                         images[c, py, px].  No atomics; one call of n views gives the bits of n calls of one view.  n == 0:
+ *                         nothing is done.
+ *   v3d_tsdf_normalize_f32  tsdf_out = tsdf_sum / weight where weight > 0, tsdf_sum elsewhere; color_out [3, n_vox] likewise from
+ *                         color_sum (both NULL: no colour).
+ * Both are asynchronous on `stream`, allocate nothing and never synchronise.  Host-side errors: V3D_ERR_BAD_ARG for a null
+ * pointer, a voxel size or truncation margin that is not positive and finite, images without a colour volume (or the reverse);
+ * V3D_ERR_BAD_SHAPE for a count that is not positive or nx ny nz >= 2^31. */
+int v3d_tsdf_integrate_f32(float* tsdf, float* weight, float* color, int nx, int ny, int nz, double voxel_size,
+                           const float* origin_host, double trunc_margin, const float* projections, const float* depths,
+                           const float* images, int n, int h, int w, void* stream);
+int v3d_tsdf_normalize_f32(const float* tsdf_sum, const float* weight, const float* color_sum, int n_vox, float* tsdf_out,
+                           float* color_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

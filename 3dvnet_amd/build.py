@@ -78,6 +78,8 @@ def build(force=False, verbose=False, strict=False):
             isa_check.check_no_scratch(os.path.join(objdir, 'tsdf.o'), 'tsdf_integrate_kernel', strict=strict)
             # nearest neighbour: the per-query search state of nn_query_kernel stays in registers
             isa_check.check_no_scratch(os.path.join(objdir, 'cloudmetrics.o'), 'nn_query_kernel', strict=strict)
+            # mesh extraction: the status bytes of a cell, its table row and the vertex state stay in registers
+            isa_check.check_no_scratch(os.path.join(objdir, 'mesh.o'), 'mc_[a-z_]*_kernel', strict=strict)
         finally:
             sys.path.pop(0)
     if force or procs or linked != tag or _stale(LIB, objs):

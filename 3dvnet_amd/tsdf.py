@@ -8,10 +8,13 @@ volume with weights and colours (``mv3d/eval/tsdf_atlas.py``: ``TSDFFusion`` :34
   * ``TSDF``                 the holder with ``to`` / ``save`` / ``load`` and the reference's npz keys;
   * ``projection_matrices``  K [R | t] (processresults.py:19-24);
   * ``volume_bounds``        the scene's volume from the quantiles of the back-projected depths (:324-357);
-  * ``fuse_preds_tsdf``      from a ``preds.npz`` record (path or mapping) to the ``TSDF``.
+  * ``fuse_preds_tsdf``      from a ``preds.npz`` record (path or mapping) to the ``TSDF``;
+  * ``TSDF.get_mesh``        the volume -> a ``mesh.TriangleMesh`` on the device (``csrc/mesh.hip``: marching cubes with the
+                             project's own case table and the reference's rules around it, tsdf_atlas.py:161-253);
+  * ``tsdf_mesh_metrics``    the rest of the ``run_tsdf`` branch (:383-397): mesh -> vertices -> down-sample -> 3D metrics.
 
-There is no CPU fallback: without the library or a HIP device every integrating entry raises ``V3DLibraryError``.
-Meshes (marching cubes), ``TSDF.transform`` and the label volume are not provided.
+There is no CPU fallback: without the library or a HIP device every integrating or meshing entry raises ``V3DLibraryError``.
+``TSDF.transform``, the label volume, ``trim_mesh`` and ``MASK_USING_GT_MESH`` are not provided.
 """
 import ctypes
 
@@ -21,6 +24,8 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import fusion as _fusion
+from . import mesh as _mesh
+from . import metrics3d as _metrics3d
 
 
 def projection_matrices(K, poses):
@@ -82,9 +87,8 @@ class TSDF:
 
     ``save`` writes the reference's npz keys: ``origin``, ``voxel_size``, ``tsdf`` and one key per attribute volume /
     attribute.  ``load`` reads them back the way the reference does, including its placement of ``weight`` (and
-    ``tsdf_point_cloud``) under ``attributes`` rather than ``attribute_vols``.  The reference's ``tsdf_point_cloud`` attribute
-    (a coloured marching-cubes vertex list ``get_tsdf`` attaches) needs marching cubes and is never produced here;
-    ``get_mesh`` and ``transform`` are not provided."""
+    ``tsdf_point_cloud``) under ``attributes`` rather than ``attribute_vols``.  ``get_mesh`` runs on the device;
+    ``transform`` is not provided."""
 
     def __init__(self, voxel_size, origin, tsdf_vol, attribute_vols=None, attributes=None):
         self.voxel_size = voxel_size
@@ -127,6 +131,19 @@ class TSDF:
         self.attributes = {key: value.to(device) for key, value in self.attributes.items()}
         self.device = device
         return self
+
+    def get_mesh(self, attribute='color'):
+        """The reference's ``get_mesh`` (tsdf_atlas.py:161-253) -> ``mesh.TriangleMesh`` on the volume's device: values
+        clamped to [-1, 1]; an empty mesh when the clamped minimum is >= 0 or the maximum <= 0; one vertex per sign-changing
+        grid edge; vertices at a -1 / +1 crossing removed together with their triangles and the rest renumbered in order;
+        ``attribute='color'`` with a colour volume: ``color[:, round(vertex)]`` clamped to [0, 255] as bytes in channel order
+        [2, 1, 0] (without a colour volume the mesh has no colours, where the reference fails).  The triangulation is this
+        project's.  ``attribute='instance'`` (the label colouring) is not provided."""
+        if attribute == 'instance':
+            raise NotImplementedError('TSDF.get_mesh: the instance colouring needs the label volume, which is not provided')
+        color = self.attribute_vols.get('color') if attribute == 'color' else None
+        verts, colors, tris = _mesh.extract(self.tsdf_vol, color, self.voxel_size, self.origin, _mesh.MODE_MESH)
+        return _mesh.TriangleMesh(verts, tris, colors)
 
 
 class TSDFFusion:
@@ -203,10 +220,13 @@ class TSDFFusion:
         self.integrate_batch(torch.as_tensor(projection)[None], torch.as_tensor(depth)[None],
                              None if color is None else torch.as_tensor(color)[None])
 
-    def get_tsdf(self):
+    def get_tsdf(self, point_cloud=False):
         """-> ``TSDF`` with the averaged distances [nx, ny, nz] (sum / weight where weight > 0, the fill value elsewhere),
-        ``attribute_vols['weight']`` and, with colour, ``['color']`` [3, nx, ny, nz] averaged the same way.  The reference's
-        ``tsdf_point_cloud`` attribute is left out (marching cubes)."""
+        ``attribute_vols['weight']`` and, with colour, ``['color']`` [3, nx, ny, nz] averaged the same way.
+        ``point_cloud=True`` with colour also attaches the reference's ``attribute_vols['tsdf_point_cloud']`` (:465-481):
+        [V, 6] float64 on the device, world x y z of every marching-cubes vertex and floor(colour at round(vertex)) in
+        channel order; the values are the kernel's fp32 / byte results.  Off by default: it costs a pass over the volume and
+        one read-back, and ``save`` would write it."""
         lib = self._lib('TSDFFusion.get_tsdf')
         nx, ny, nz = self._dims
         tsdf_vol = torch.empty_like(self.tsdf_vol)
@@ -218,6 +238,10 @@ class TSDFFusion:
         attribute_vols = {'weight': self.weight_vol.view(nx, ny, nz)}
         if color_vol is not None:
             attribute_vols['color'] = color_vol.view(3, nx, ny, nz)
+            if point_cloud:
+                verts, colors, _ = _mesh.extract(tsdf_vol.view(nx, ny, nz), attribute_vols['color'], self.voxel_size, self.origin,
+                                                 _mesh.MODE_POINT_CLOUD)
+                attribute_vols['tsdf_point_cloud'] = torch.cat((verts.double(), colors.double()), dim=1)
         return TSDF(self.voxel_size, self.origin, tsdf_vol.view(nx, ny, nz), attribute_vols)
 
 
@@ -254,3 +278,34 @@ def fuse_preds_tsdf(preds, images, vox_res=.04, trunc_ratio=3, vol_prcnt=.995, v
         fus.integrate_batch(projection_matrices(K[sl], poses[sl]), depths[sl], images[sl] if color else None)
     tsdf = fus.get_tsdf()
     return (tsdf, fus) if return_fusion else tsdf
+
+
+def tsdf_mesh_metrics(preds, images, gt_points, vox_res=.04, trunc_ratio=3, voxel_downsample=0.02, dist_thresh=0.05,
+                      vol_prcnt=.995, vol_margin=1.5, img_batch=100, device=None, return_mesh=False):
+    """The ``run_tsdf`` branch to its end (processresults.py:297-397) without files or GT-mesh masking: ``fuse_preds_tsdf``
+    -> ``get_mesh`` -> the mesh's vertices through ``metrics3d.voxel_down_sample`` -> ``metrics3d.eval_clouds`` against the
+    down-sampled ``gt_points`` [n, 3].  -> the dict of the five metrics and ``'n'`` (the number of views);
+    ``return_mesh=True`` -> ``(dict, TriangleMesh)``.  An empty mesh or ground truth gives NaN metrics, as the reference's
+    NumPy means do.  The vertices never leave the device; read-backs: the mesh's two counts, the two down-sampled counts and
+    the final 40-byte record."""
+    _lib.load()
+    dev = _fusion._device(device)
+    if isinstance(preds, (str, bytes)) or hasattr(preds, '__fspath__'):
+        with np.load(preds) as f:
+            preds = {k: f[k] for k in f.files}
+    n_views = int(np.asarray(preds['depth_preds']).shape[0])
+    tsdf = fuse_preds_tsdf(preds, images, vox_res, trunc_ratio, vol_prcnt, vol_margin, img_batch, color=True, device=dev)
+    mesh = tsdf.get_mesh()
+    out = {k: float('nan') for k in _metrics3d.KEYS}
+    gt = _metrics3d._to_device(_metrics3d._points(gt_points), dev)
+    if mesh.vertices.shape[0] > 0 and gt.shape[0] > 0:
+        pred, _, n_pred = _metrics3d.voxel_down_sample(mesh.vertices, voxel_downsample)
+        trgt, _, n_trgt = _metrics3d.voxel_down_sample(gt, voxel_downsample)
+        n_pred, n_trgt = int(n_pred.item()), int(n_trgt.item())
+        for c in (n_pred, n_trgt):
+            if c < 0:
+                _metrics3d._raise_status(-c)
+        if n_pred > 0 and n_trgt > 0:
+            out = dict(zip(_metrics3d.KEYS, _metrics3d.eval_clouds(pred[:n_pred], trgt[:n_trgt], dist_thresh).cpu().tolist()))
+    out['n'] = n_views
+    return (out, mesh) if return_mesh else out

@@ -553,6 +553,45 @@ int v3d_tsdf_integrate_f32(float* tsdf, float* weight, float* color, int nx, int
 int v3d_tsdf_normalize_f32(const float* tsdf_sum, const float* weight, const float* color_sum, int n_vox, float* tsdf_out,
                            float* color_out, void* stream);
 
+/* Triangle meshes from TSDF volumes (csrc/mesh.hip): marching cubes with the project's own case table (csrc/mc_table.h, generated
+ * from a rule by scripts/gen_mc_table.py) and what mv3d/eval/tsdf_atlas.py does around its marching-cubes call.  ABI version:
+ * STILL 9 (additive, as the TSDF symbols are).
+ *   Volume: tsdf [nx, ny, nz] fp32, z fastest (flat index (x ny + y) nz + z), as v3d_tsdf_normalize_f32 leaves it; values are
+ *   clamped to [-1, 1] on load (a NaN stays a NaN).  A voxel is inside iff its clamped value is < 0 (NaN and -0.0: outside).
+ *   color [3, nx ny nz] fp32 (may be NULL).
+ *   Vertices: one per sign-changing grid edge, ordered by the owning voxel's flat index, then by axis x, y, z (a voxel owns the
+ *   edges that leave it in +x, +y, +z and stay inside the volume).  For the edge from voxel a to its +axis neighbour b, all fp32:
+ *   t = va / (va - vb), index coordinate = fl(i + t), world = fl(fl(index * voxel_size) + origin).
+ *   Triangles: ordered by the flat index of the cell's lowest voxel, then in table order; indices into the FINAL vertex list.
+ *   mode V3D_MESH_MODE_MESH = TSDF.get_mesh (:161-253): a vertex is BAD when, among the eight clamped values at floor(index
+ *     coordinate) + {0, 1}^3 (clipped to the volume), one equals +1 and one equals -1; bad vertices and every triangle that
+ *     references one are dropped, the rest is renumbered in order.  Colour = color[:, round-half-even(index coordinate)] clamped
+ *     to [0, 255], truncated to a byte, stored in channel order [2, 1, 0].  Empty-mesh rule: no vertex and no triangle when the
+ *     minimum of the clamped volume is >= 0 or its maximum is <= 0.
+ *   mode V3D_MESH_MODE_POINT_CLOUD = the tsdf_point_cloud attribute of get_tsdf (:465-481): every vertex, no triangles, no
+ *     empty-mesh rule; colour = floor(color[:, round(index coordinate)]) as a byte, channel order [0, 1, 2].
+ * Two calls, and ONE read-back between them:
+ *   v3d_mesh_count_f32    classifies the volume in `workspace` (v3d_mesh_workspace_bytes) and writes the number of vertices and
+ *                         triangles to the DEVICE words counts[0], counts[1] (both -1 when a total reaches 2^31).  The caller
+ *                         reads the two words to size the outputs.
+ *   v3d_mesh_extract_f32  with the SAME volume, mode and workspace, untouched since the count call: writes verts [v_cap, 3] fp32,
+ *                         colors [v_cap, 3] bytes (NULL exactly when color is NULL) and tris [f_cap, 3] int32.  v_cap / f_cap are
+ *                         the rows the outputs hold, normally the two counts; rows beyond a capacity are not written (no status
+ *                         word: the counts are known).  A capacity of 0 skips that output.  origin [3] and voxel_size are taken
+ *                         as fp32 (origin: HOST, read before the call returns).
+ * Both are asynchronous on `stream`, allocate nothing and never synchronise; no atomics, so repeated calls give identical bits.
+ * Host-side errors: V3D_ERR_BAD_ARG for a null required pointer, an unknown mode, a voxel size that is not positive and finite,
+ * a colour volume without a colour output (or the reverse); V3D_ERR_BAD_SHAPE for a dimension that is not positive, nx ny nz >=
+ * 2^31 or a negative capacity; V3D_ERR_WORKSPACE_TOO_SMALL. */
+#define V3D_MESH_MODE_MESH 0
+#define V3D_MESH_MODE_POINT_CLOUD 1
+size_t v3d_mesh_workspace_bytes(int nx, int ny, int nz);
+int v3d_mesh_count_f32(const float* tsdf, int nx, int ny, int nz, int mode, int32_t* counts, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int v3d_mesh_extract_f32(const float* tsdf, const float* color, int nx, int ny, int nz, double voxel_size,
+                         const float* origin_host, int mode, float* verts, uint8_t* colors, int v_cap, int32_t* tris, int f_cap,
+                         const void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

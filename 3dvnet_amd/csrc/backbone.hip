@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "v3d_common.h"
+#include "weight_pack.h"
 
 struct v3d_conv_weights {
   int cout, k, ncb, nsteps;      // output channels, K = taps * Cin, column blocks of 32, K steps of 8
@@ -288,19 +289,10 @@ extern "C" int v3d_conv_pack(const float* w_host, const float* bias_host, int co
           host[(((size_t)cb * h->nsteps + s) * 64 + lane) * 4 + m] = co < cout ? w_host[(size_t)co * k + kq] : 0.f;
         }
   for (int co = 0; co < cout; ++co) host[h->bias_ofs + co] = bias_host ? bias_host[co] : 0.f;
-  hipError_t e = hipMalloc((void**)&h->dev, host.size() * sizeof(float));
-  if (e != hipSuccess) { delete h; return v3d::fail(V3D_ERR_HIP, "hipMalloc(conv weights): %s", hipGetErrorString(e)); }
-  e = hipMemcpy(h->dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void)hipFree(h->dev); delete h; return v3d::fail(V3D_ERR_HIP, "hipMemcpy(conv weights): %s", hipGetErrorString(e)); }
-  *out_handle = h;
-  return V3D_OK;
+  return v3d::finish_pack(h, host.data(), host.size() * sizeof(float), "conv weights", out_handle);
 }
 
-extern "C" void v3d_conv_free(v3d_conv_weights* h) {
-  if (!h) return;
-  if (h->dev) (void)hipFree(h->dev);
-  delete h;
-}
+extern "C" void v3d_conv_free(v3d_conv_weights* h) { v3d::release(h); }
 
 extern "C" int v3d_conv_nhwc_f32(const v3d_conv_weights* h, const float* x, int n, int H, int W, int cin, int taps, int relu,
                                  int res_mode, const float* res, float* out, void* stream) {

@@ -21,6 +21,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "bf16_split.h"
 #include "v3d_common.h"
 
 namespace {
@@ -54,15 +55,6 @@ struct CZParams {
   int n, D, H, W, nty, ntx, nseg, seg_len, n_tasks;
 };
 
-__device__ __forceinline__ unsigned cz_bf16_rne(float x) {
-  unsigned u = __float_as_uint(x);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ unsigned cz_pack_bf16x2(float a, float b) {
-  typedef float f32x2_ __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_){a, b}, bf16x2_));
-}
 __device__ __forceinline__ float cz_lane_select(int cond, float a, float b) {
   const unsigned m = 0u - (unsigned)(cond != 0);
   return __uint_as_float((__float_as_uint(a) & m) | (__float_as_uint(b) & ~m));
@@ -419,9 +411,9 @@ __global__ __launch_bounds__(512, 2) void conv0z_kernel(CZParams p) {
           for (int r = 0; r < 4; ++r) val[r] = fmaxf(v[r] + bias[r], 0.f);
           // hi = RNE_bf16(x), lo = RNE_bf16(x - hi) on packed pairs (v_cvt_pk_bf16_f32: the same rounding as the shift
           // arithmetic of the other kernels for finite values)
-          const unsigned h01 = cz_pack_bf16x2(val[0], val[1]), h23 = cz_pack_bf16x2(val[2], val[3]);
-          const unsigned l01 = cz_pack_bf16x2(val[0] - __uint_as_float(h01 << 16), val[1] - __uint_as_float(h01 & 0xffff0000u));
-          const unsigned l23 = cz_pack_bf16x2(val[2] - __uint_as_float(h23 << 16), val[3] - __uint_as_float(h23 & 0xffff0000u));
+          const unsigned h01 = v3d::pack_bf16x2(val[0], val[1]), h23 = v3d::pack_bf16x2(val[2], val[3]);
+          const unsigned l01 = v3d::pack_bf16x2(val[0] - __uint_as_float(h01 << 16), val[1] - __uint_as_float(h01 & 0xffff0000u));
+          const unsigned l23 = v3d::pack_bf16x2(val[2] - __uint_as_float(h23 << 16), val[3] - __uint_as_float(h23 & 0xffff0000u));
           if (fok[k]) {
             const size_t sp = (size_t)zo * HW + fsp[k];
             if constexpr (F32) {
@@ -498,13 +490,9 @@ int v3d::launch_conv0z(bool f32, const void* in, const float* wimg, const float*
   const long long tasks = tiles * p.nseg;
   V3D_REQUIRE(tasks > 0 && tasks < (1ll << 31), V3D_ERR_BAD_SHAPE, "conv0: bad grid");
   p.n_tasks = (int)tasks;
-  static bool attr_set[64][2] = {{false}};
-  V3D_REQUIRE(dev >= 0 && dev < 64, V3D_ERR_UNSUPPORTED, "conv0: device ordinal %d", dev);
-  if (!attr_set[dev][f32]) {
-    V3D_CHECK_HIP(hipFuncSetAttribute(f32 ? (const void*)conv0z_kernel<true> : (const void*)conv0z_kernel<false>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, CZ::LDS_BYTES));
-    attr_set[dev][f32] = true;
-  }
+  static bool lds_opted[2][64] = {};
+  if (const int rc = v3d::opt_in_dynamic_lds(f32 ? (const void*)conv0z_kernel<true> : (const void*)conv0z_kernel<false>, CZ::LDS_BYTES,
+                                             lds_opted[f32]); rc != V3D_OK) return rc;
   {
     v3d::TimedScope ts("costreg_conv0", s);
     if (f32) conv0z_kernel<true><<<v3d::persistent_grid(tasks, 1), 512, CZ::LDS_BYTES, s>>>(p);

@@ -28,6 +28,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "bf16_split.h"
 #include "v3d_common.h"
 
 namespace {
@@ -65,18 +66,6 @@ struct C12Params {
   void* out;           // conv2 output, split layout [n][2 groups][hi, lo][D2][H2][W2]
   int n, D, H, W, D2, H2, W2, nty, ntx, nseg, seg_len, n_tasks;
 };
-
-__device__ __forceinline__ unsigned c12_pack(float a, float b) {
-  typedef float f32x2_ __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_){a, b}, bf16x2_));
-}
-__device__ __forceinline__ void c12_split4(const float (&v)[4], u32x2& hi, u32x2& lo) {
-  const unsigned h01 = c12_pack(v[0], v[1]), h23 = c12_pack(v[2], v[3]);
-  hi = (u32x2){h01, h23};
-  lo = (u32x2){c12_pack(v[0] - __uint_as_float(h01 << 16), v[1] - __uint_as_float(h01 & 0xffff0000u)),
-               c12_pack(v[2] - __uint_as_float(h23 << 16), v[3] - __uint_as_float(h23 & 0xffff0000u))};
-}
 
 // f(integral_constant<int, I>) for I = B .. E - 1, fully unrolled with compile-time indices
 template <int B, int E, class F>
@@ -488,7 +477,7 @@ __global__ __launch_bounds__(512, 2) void conv12z_kernel(C12Params p, const floa
 #pragma unroll
           for (int r = 0; r < 4; ++r) val[r] = fmaxf(v[r] + bias[r], 0.f);
           u32x2 hi, lo;
-          c12_split4(val, hi, lo);
+          v3d::split4(val[0], val[1], val[2], val[3], hi, lo);
           if (fok[k]) {
             const size_t sp = (size_t)zo * HW2 + fsp[k];
             outs[sp * 2] = hi;
@@ -533,7 +522,7 @@ __global__ __launch_bounds__(512, 2) void conv12z_kernel(C12Params p, const floa
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = (plane_in1 && ((inside >> b) & 1u)) ? fmaxf(a[r] + bias1[r], 0.f) : 0.f;
             u32x2 hi, lo;
-            c12_split4(v, hi, lo);
+            v3d::split4(v[0], v[1], v[2], v[3], hi, lo);
             *reinterpret_cast<u32x2*>(dst + woff[b]) = hi;
             *reinterpret_cast<u32x2*>(dst + woff[b] + C12::HL1) = lo;
           }
@@ -584,12 +573,8 @@ int v3d::launch_conv12z(const void* c0, const float* w1, const float* w2, const 
   const long long tasks = tiles * p.nseg;
   V3D_REQUIRE(tasks > 0 && tasks < (1ll << 31), V3D_ERR_BAD_SHAPE, "conv1+conv2: bad grid");
   p.n_tasks = (int)tasks;
-  static bool attr_set[64] = {false};
-  V3D_REQUIRE(dev >= 0 && dev < 64, V3D_ERR_UNSUPPORTED, "conv1+conv2: device ordinal %d", dev);
-  if (!attr_set[dev]) {
-    V3D_CHECK_HIP(hipFuncSetAttribute((const void*)conv12z_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, C12::LDS_BYTES));
-    attr_set[dev] = true;
-  }
+  static bool lds_opted[64] = {};
+  if (const int rc = v3d::opt_in_dynamic_lds((const void*)conv12z_kernel, C12::LDS_BYTES, lds_opted); rc != V3D_OK) return rc;
   {
     v3d::TimedScope ts("costreg_conv12", s);
     conv12z_kernel<<<v3d::persistent_grid(tasks, 1), 512, C12::LDS_BYTES, s>>>(p, b1, b2);

@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "v3d_common.h"
+#include "weight_pack.h"
 
 #ifndef V3D_ABLATE
 #define V3D_ABLATE 0   // developer ablations of the conv kernel (1: no MFMA loop, 2: no restaging)
@@ -613,22 +614,8 @@ __device__ __forceinline__ float lane_select(int cond, float a, float b) {
   return __uint_as_float((__float_as_uint(a) & m) | (__float_as_uint(b) & ~m));
 }
 
-__device__ __forceinline__ unsigned bf16_rne(float x) {
-  unsigned u = __float_as_uint(x);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-// The same split on packed pairs (v_cvt_pk_bf16_f32: round to nearest even in hardware, the bits of bf16_rne for finite values;
-// psv_variance.hip / conv0z.hip / conv12z.hip use it too): 12 instead of ~50 vector instructions per four values in the epilogues
-__device__ __forceinline__ unsigned cr_pack_bf16x2(float a, float b) {
-  typedef float f32x2_ __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_){a, b}, bf16x2_));
-}
-__device__ __forceinline__ void split4(float a, float b, float c, float d, u32x2& hp, u32x2& lp) {
-  hp = (u32x2){cr_pack_bf16x2(a, b), cr_pack_bf16x2(c, d)};
-  lp = (u32x2){cr_pack_bf16x2(a - __uint_as_float(hp.x << 16), b - __uint_as_float(hp.x & 0xffff0000u)),
-               cr_pack_bf16x2(c - __uint_as_float(hp.y << 16), d - __uint_as_float(hp.y & 0xffff0000u))};
-}
+using v3d::bf16_rne;      // bf16_split.h: the split x = hi + lo, one value at a time and on packed pairs
+using v3d::split4;
 
 // SPLIT_IN: `p.in` is the split-bf16 volume written by psv_variance_kernel<32, true>
 // ([n][4 chunks][hi, lo][D][H][W] 16-byte slots): staging is then 16-byte copies, no conversion.
@@ -1927,21 +1914,11 @@ int launch_conv0_bf16(bool split_in, bool split_out, const float* in, const floa
   const long long blocks = (long long)n * p.ntz * p.nty * p.ntx;
   V3D_REQUIRE(blocks > 0 && blocks < (1ll << 31), V3D_ERR_BAD_SHAPE, "conv0: bad grid");
   V3D_REQUIRE((long long)8 * Di * Hi * Wi < (1ll << 31), V3D_ERR_BAD_SHAPE, "conv0: input volume too large");
-  static bool attr_set[64] = {false};      // per device: the dynamic-LDS opt-in is a per-device function attribute
-  int attr_dev = 0;
-  V3D_CHECK_HIP(hipGetDevice(&attr_dev));
-  V3D_REQUIRE(attr_dev >= 0 && attr_dev < 64, V3D_ERR_UNSUPPORTED, "device ordinal %d", attr_dev);
-  if (!attr_set[attr_dev]) {
-    V3D_CHECK_HIP(hipFuncSetAttribute((const void*)conv0_bf16x2_kernel<false, false, 4>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)C0::LDS_BYTES));
-    V3D_CHECK_HIP(hipFuncSetAttribute((const void*)conv0_bf16x2_kernel<true, false, 4>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)C0::LDS_BYTES));
-    V3D_CHECK_HIP(hipFuncSetAttribute((const void*)conv0_bf16x2_kernel<true, true, kC0Waves>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)C0::LDS_BYTES));
-    V3D_CHECK_HIP(hipFuncSetAttribute((const void*)conv0_bf16x2_kernel<false, true, 4>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)C0::LDS_BYTES));
-    attr_set[attr_dev] = true;
-  }
+  static bool lds_opted[4][64] = {};
+  const void* const kernels[4] = {(const void*)conv0_bf16x2_kernel<false, false, 4>, (const void*)conv0_bf16x2_kernel<true, false, 4>,
+                                  (const void*)conv0_bf16x2_kernel<true, true, kC0Waves>, (const void*)conv0_bf16x2_kernel<false, true, 4>};
+  for (int k = 0; k < 4; ++k)
+    if (const int rc = v3d::opt_in_dynamic_lds(kernels[k], (int)C0::LDS_BYTES, lds_opted[k]); rc != V3D_OK) return rc;
   {
     v3d::TimedScope ts("costreg_conv0", s);
 #ifdef V3D_C0_PERSIST       // developer A/B: 512 resident workgroups walking their tiles (same time, 15 % more halo traffic)
@@ -1979,15 +1956,8 @@ int launch_convg(const char* name, const void* in, const float* wbf, const float
   // the output side indexes 4 planes from the item's base
   V3D_REQUIRE(Di < (1 << 12) && Hi < (1 << 12) && Wi < (1 << 12) && (long long)Di * Hi * Wi < (1ll << 24), V3D_ERR_BAD_SHAPE,
               "%s: volume %d x %d x %d too large for 32-bit slot offsets", name, Di, Hi, Wi);
-  static bool attr_set[64] = {false};      // per device: the dynamic-LDS opt-in is a per-device function attribute
-  int attr_dev = 0;
-  V3D_CHECK_HIP(hipGetDevice(&attr_dev));
-  V3D_REQUIRE(attr_dev >= 0 && attr_dev < 64, V3D_ERR_UNSUPPORTED, "device ordinal %d", attr_dev);
-  if (!attr_set[attr_dev]) {
-    V3D_CHECK_HIP(hipFuncSetAttribute((const void*)convg_bf16x2_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)C::LDS_BYTES));
-    attr_set[attr_dev] = true;
-  }
+  static bool lds_opted[64] = {};
+  if (const int rc = v3d::opt_in_dynamic_lds((const void*)convg_bf16x2_kernel<C>, (int)C::LDS_BYTES, lds_opted); rc != V3D_OK) return rc;
   {
     v3d::TimedScope ts(name, s);
     unsigned grid = (unsigned)((blocks * C::NCG + 7) / 8 * 8);        // one (tile, channel group) item per workgroup ...
@@ -2039,6 +2009,142 @@ struct v3d_costreg_weights {
   size_t wp_ofs[10], bias_ofs[10], prob_w2_ofs, prob_b_ofs, c0bf_ofs, c0f32_ofs, cgbf_ofs[7], dgbf_ofs[2], c9bf_ofs, c9f32_ofs, total;
 };
 
+// ---- weight images: one function per image family.  Each takes the BN-folded weights of its layer (in the layout of the
+// layer's conv_w) and holds the family's lane -> (row, k) map; the split itself is v3d::split_bf16x8, whose hi words land at
+// the lane's place in the [hi, lo][lane 64][4 words] block and whose lo words follow 256 words later. ----
+namespace {
+constexpr int kLoWords = 64 * 4;
+
+size_t tile_image_floats(const LayerDesc& L) {
+  const bool pair = L.mode == kConvS1Pair;
+  return (size_t)(L.cin / L.ck) * (9 * (pair ? 4 : 3)) * (L.ck / 4) * (pair ? 1 : (L.cout + 15) / 16) * 64;
+}
+
+// exact-fp32 fragment image of a layer for conv3d_mfma_kernel: [chunk][tap][4-channel step][16-row block][lane 64]
+void pack_tile_image(const LayerDesc& L, const float* w, float* wp) {
+  const bool pair = L.mode == kConvS1Pair;
+  const int MB = pair ? 1 : (L.cout + 15) / 16, C4 = L.ck / 4, nchunk = L.cin / L.ck;
+  const int KXN = pair ? 4 : 3, NT = 9 * KXN;
+  for (int chunk = 0; chunk < nchunk; ++chunk)
+    for (int tap = 0; tap < NT; ++tap)
+      for (int c4 = 0; c4 < C4; ++c4)
+        for (int m = 0; m < MB; ++m)
+          for (int lane = 0; lane < 64; ++lane) {
+            const int row = m * 16 + (lane & 15);
+            const int ci = chunk * L.ck + c4 * 4 + (lane >> 4);
+            float v = 0.f;
+            if (pair) {
+              // row = x-shift * 8 + channel; virtual tap = (kz, ky, kx') with kx' in 0..3
+              const int sx = row >> 3, co = row & 7, kzy = tap / 4, kx = tap % 4 - sx;
+              if (kx >= 0 && kx <= 2) v = w[((size_t)co * L.cin + ci) * 27 + kzy * 3 + kx];
+            } else if (row < L.cout) {
+              // Conv3d weight [Co, Ci, 3,3,3]; ConvTranspose3d weight [Ci, Co, 3,3,3]
+              v = w[L.mode == kDeconvS2 ? ((size_t)ci * L.cout + row) * 27 + tap : ((size_t)row * L.cin + ci) * 27 + tap];
+            }
+            wp[((((size_t)chunk * NT + tap) * C4 + c4) * MB + m) * 64 + lane] = v;
+          }
+}
+
+// conv0 in pair mode, lane (kx', row): row = x shift * 8 + co, kx = kx' - x shift of the 4-wide window; 0 where the shifted
+// kernel does not reach and for input channels the net does not have (16 input channels: chunks 2, 3 carry zero weights)
+float conv0_pair_weight(const float* w, int in_channels, int lane, int kzy, int ci) {
+  const int row = lane & 15, kxp = lane >> 4, sx = row >> 3, co = row & 7, kx = kxp - sx;
+  return kx >= 0 && kx <= 2 && ci < in_channels ? w[((size_t)co * in_channels + ci) * 27 + kzy * 3 + kx] : 0.f;
+}
+
+// split-bf16 image of conv0 for conv0_bf16x2_kernel / conv0z_kernel<false>: [chunk 4][kzy 9][hi, lo][lane 64][4 words]
+void pack_conv0_split(const float* w, int in_channels, unsigned* wb) {
+  for (int chunk = 0; chunk < C0::NCH; ++chunk)
+    for (int kzy = 0; kzy < 9; ++kzy)
+      for (int lane = 0; lane < 64; ++lane) {
+        float v[8];
+        for (int e = 0; e < 8; ++e) v[e] = conv0_pair_weight(w, in_channels, lane, kzy, chunk * 8 + e);
+        unsigned* dst = wb + ((size_t)chunk * 9 + kzy) * 2 * kLoWords + lane * 4;
+        v3d::split_bf16x8(v, dst, dst + kLoWords);
+      }
+}
+
+// exact-fp32 image of conv0 for conv0z_kernel<true> (v_mfma_f32_16x16x4_f32, pair mode): [chunk 4][kz * 3 + ky][channel 8]
+// [lane 64]; lane (kq, m): row m = x shift * 8 + co, k = x tap kq of the 4-wide window
+void pack_conv0_f32(const float* w, int in_channels, float* wf) {
+  for (int chunk = 0; chunk < 4; ++chunk)
+    for (int kzy = 0; kzy < 9; ++kzy)
+      for (int e = 0; e < 8; ++e)
+        for (int lane = 0; lane < 64; ++lane)
+          wf[(((size_t)chunk * 9 + kzy) * 8 + e) * 64 + lane] = conv0_pair_weight(w, in_channels, lane, kzy, chunk * 8 + e);
+}
+
+// conv9 for conv9_prob_kernel, w = ConvTranspose3d weight [16][8][27].  Split-bf16 image: [block 9][hi, lo][lane 64][4 words];
+// block = tz3 * 3 + ty3 with t?3 = {(parity 0, input 0), (0, 1), (1, 1)} <-> kernel tap {2, 0, 1}; rows = x parity * 8 + co,
+// k = x input * 16 + ci.  fp32 image of the same GEMM for conv9_prob_kernel<true>: [block 9][half 2][lane 64][4]; k slice
+// sl = half * 4 + q of v_mfma_f32_16x16x4_f32, lane group kq: k = 4 sl + kq = x input * 16 + ci
+void pack_conv9(const float* w, unsigned* wb, float* wf) {
+  static const int tap3[3] = {2, 0, 1};
+  auto weight = [&](int blk, int m, int k) {      // row m, k = x input * 16 + ci of block blk
+    const int px = m >> 3, co = m & 7, dx = k >> 4, ci = k & 15;
+    const int kz = tap3[blk / 3], ky = tap3[blk % 3];
+    const int kx = px == 0 ? (dx == 0 ? 2 : 0) : (dx == 1 ? 1 : -1);
+    return kx < 0 ? 0.f : w[((size_t)ci * 8 + co) * 27 + kz * 9 + ky * 3 + kx];
+  };
+  for (int blk = 0; blk < 9; ++blk)
+    for (int lane = 0; lane < 64; ++lane) {
+      float v[8];
+      for (int e = 0; e < 8; ++e) v[e] = weight(blk, lane & 15, (lane >> 4) * 8 + e);
+      unsigned* dst = wb + (size_t)blk * 2 * kLoWords + lane * 4;
+      v3d::split_bf16x8(v, dst, dst + kLoWords);
+    }
+  for (int blk = 0; blk < 9; ++blk)
+    for (int sl = 0; sl < 8; ++sl)
+      for (int lane = 0; lane < 64; ++lane)
+        wf[(((size_t)blk * 2 + (sl >> 2)) * 64 + lane) * 4 + (sl & 3)] = weight(blk, lane & 15, 4 * sl + (lane >> 4));
+}
+
+// split-bf16 image of conv1..conv6 for convg_bf16x2_kernel: [cout group][8-channel chunk][kz, ky][hi, lo][lane 64]
+// [4 words]; rows = output channel within the group, k = 8 * x tap + ci (x tap 3 = 0)
+void pack_convg(const float* w, int cin, int cout, unsigned* wb) {
+  const int nch = cin / 8, ncg = cout / 16;
+  for (int g = 0; g < ncg; ++g)
+    for (int ch = 0; ch < nch; ++ch)
+      for (int kzy = 0; kzy < 9; ++kzy)
+        for (int lane = 0; lane < 64; ++lane) {
+          const int co = g * 16 + (lane & 15), kx = lane >> 4;
+          float v[8];
+          for (int e = 0; e < 8; ++e) v[e] = kx > 2 ? 0.f : w[((size_t)co * cin + ch * 8 + e) * 27 + kzy * 3 + kx];
+          unsigned* dst = wb + (((size_t)g * nch + ch) * 9 + kzy) * 2 * kLoWords + lane * 4;
+          v3d::split_bf16x8(v, dst, dst + kLoWords);
+        }
+}
+
+// split-bf16 image of conv7 / conv8 for deconvg_bf16x2_kernel, w = ConvTranspose3d weight [cin][cout][27]: [cout group]
+// [8-channel chunk][block 12][hi, lo][lane 64][4 words]; block = zb * 4 + (py, px), zb = {(pz 0, dz 0), (1, 0), (1, 1)};
+// rows = output channel, k = 8 * (dy, dx) + ci.  Kernel tap of (parity p, input d): p 0: d 0 -> 1; p 1: d 0 -> 2, d 1 -> 0.
+void pack_deconvg(const float* w, int cin, int cout, unsigned* wb) {
+  const int nch = cin / 8, ncg = cout / 16;
+  auto tap = [](int par, int d) { return par == 0 ? (d == 0 ? 1 : -1) : (d == 0 ? 2 : 0); };
+  for (int g = 0; g < ncg; ++g)
+    for (int ch = 0; ch < nch; ++ch)
+      for (int blk = 0; blk < 12; ++blk)
+        for (int lane = 0; lane < 64; ++lane) {
+          const int zb = blk / 4, py = (blk >> 1) & 1, px = blk & 1;
+          const int pz = zb == 0 ? 0 : 1, dz = zb == 2 ? 1 : 0;
+          const int co = g * 16 + (lane & 15), dy = lane >> 5, dx = (lane >> 4) & 1;
+          const int kz = tap(pz, dz), ky = tap(py, dy), kx = tap(px, dx);
+          float v[8];
+          for (int e = 0; e < 8; ++e)
+            v[e] = (kz < 0 || ky < 0 || kx < 0) ? 0.f : w[((size_t)(ch * 8 + e) * cout + co) * 27 + kz * 9 + ky * 3 + kx];
+          unsigned* dst = wb + (((size_t)g * nch + ch) * 12 + blk) * 2 * kLoWords + lane * 4;
+          v3d::split_bf16x8(v, dst, dst + kLoWords);
+        }
+}
+
+// prob weights for the fused kernel, channel pairs interleaved: [4 pairs][27 taps][2]
+void pack_prob(const float* prob_w, float* out) {
+  for (int cp = 0; cp < 4; ++cp)
+    for (int t = 0; t < 27; ++t)
+      for (int e = 0; e < 2; ++e) out[((size_t)cp * 27 + t) * 2 + e] = prob_w[(cp * 2 + e) * 27 + t];
+}
+}  // namespace
+
 extern "C" int v3d_costreg_pack(const float* const* conv_w, const float* const* bn_w,
                                 const float* const* bn_b, const float* const* bn_m,
                                 const float* const* bn_v, const float* prob_w, const float* prob_b,
@@ -2050,225 +2156,41 @@ extern "C" int v3d_costreg_pack(const float* const* conv_w, const float* const* 
               "v3d_costreg_pack: CostRegNet(32, 8) and CostRegNet(16, 8) are built (got %d, %d)", in_channels, base);
   v3d_costreg_weights* h = new v3d_costreg_weights();
   h->in_channels = in_channels; h->base = base;
-  std::vector<float> host;
-  auto reserve = [&](size_t nfloat) { size_t o = host.size(); host.resize(o + (nfloat + 63) / 64 * 64, 0.f); return o; };
+  v3d::HostImage img;
+  std::vector<float> wf[10];      // BN-folded weights of every layer, in the layout of conv_w[l]
   for (int l = 0; l < 10; ++l) {
     LayerDesc L = kLayers[l];
     if (l == 0) L.cin = in_channels;
-    const bool pair = L.mode == kConvS1Pair;
-    const int MB = pair ? 1 : (L.cout + 15) / 16, C4 = L.ck / 4, nchunk = L.cin / L.ck;
-    const int KXN = pair ? 4 : 3, NT = 9 * KXN;
-    h->wp_ofs[l] = reserve((size_t)nchunk * NT * C4 * MB * 64);
-    h->bias_ofs[l] = reserve(L.cout);
-    float* wp = host.data() + h->wp_ofs[l];
-    float* bias = host.data() + h->bias_ofs[l];
-    std::vector<float> scale(L.cout);
-    for (int co = 0; co < L.cout; ++co) {
-      // eval-mode BatchNorm: y = (x - mean) / sqrt(var + eps) * gamma + beta   (mvsnet.py:22,33)
-      scale[co] = bn_w[l][co] / sqrtf(bn_v[l][co] + eps);
-      bias[co] = bn_b[l][co] - bn_m[l][co] * scale[co];
-    }
-    for (int chunk = 0; chunk < nchunk; ++chunk)
-      for (int tap = 0; tap < NT; ++tap)
-        for (int c4 = 0; c4 < C4; ++c4)
-          for (int m = 0; m < MB; ++m)
-            for (int lane = 0; lane < 64; ++lane) {
-              const int row = m * 16 + (lane & 15);
-              const int ci = chunk * L.ck + c4 * 4 + (lane >> 4);
-              float v = 0.f;
-              if (pair) {
-                // row = x-shift * 8 + channel; virtual tap = (kz, ky, kx') with kx' in 0..3
-                const int sx = row >> 3, co = row & 7, kzy = tap / 4, kx = tap % 4 - sx;
-                if (kx >= 0 && kx <= 2)
-                  v = conv_w[l][((size_t)co * L.cin + ci) * 27 + kzy * 3 + kx] * scale[co];
-              } else if (row < L.cout) {
-                // Conv3d weight [Co, Ci, 3,3,3]; ConvTranspose3d weight [Ci, Co, 3,3,3]
-                const size_t idx = L.mode == kDeconvS2 ? ((size_t)ci * L.cout + row) * 27 + tap
-                                                       : ((size_t)row * L.cin + ci) * 27 + tap;
-                v = conv_w[l][idx] * scale[row];
-              }
-              wp[((((size_t)chunk * NT + tap) * C4 + c4) * MB + m) * 64 + lane] = v;
-            }
+    const v3d::BnFold bn(bn_w[l], bn_b[l], bn_m[l], bn_v[l], eps, L.cout);
+    wf[l] = L.mode == kDeconvS2 ? bn.weights(conv_w[l], L.cin, 27) : bn.weights(conv_w[l], 1, (size_t)L.cin * 27);
+    h->wp_ofs[l] = img.reserve(tile_image_floats(L));
+    h->bias_ofs[l] = img.reserve(L.cout);
+    pack_tile_image(L, wf[l].data(), img.at(h->wp_ofs[l]));
+    memcpy(img.at(h->bias_ofs[l]), bn.bias.data(), L.cout * sizeof(float));
   }
-  {
-    // split-bf16 image of conv0 for conv0_bf16x2_kernel: [chunk 4][kzy 9][hi, lo][lane 64][4 words]
-    const int l = 0;
-    h->c0bf_ofs = reserve((size_t)C0::NCH * C0::WU32);
-    unsigned* wb = reinterpret_cast<unsigned*>(host.data() + h->c0bf_ofs);
-    auto rne = [](float x) { unsigned u; memcpy(&u, &x, 4); return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16; };
-    auto up = [](unsigned hb) { unsigned u = hb << 16; float f; memcpy(&f, &u, 4); return f; };
-    for (int chunk = 0; chunk < C0::NCH; ++chunk)
-      for (int kzy = 0; kzy < 9; ++kzy)
-        for (int lane = 0; lane < 64; ++lane) {
-          const int row = lane & 15, kxp = lane >> 4, sx = row >> 3, co = row & 7, kx = kxp - sx;
-          unsigned hi[8], lo[8];
-          for (int e = 0; e < 8; ++e) {
-            const int ci = chunk * 8 + e;
-            float v = 0.f;
-            if (kx >= 0 && kx <= 2 && ci < in_channels) {        // (16 input channels: chunks 2, 3 carry zero weights)
-              const float sc = bn_w[l][co] / sqrtf(bn_v[l][co] + eps);
-              v = conv_w[l][((size_t)co * in_channels + ci) * 27 + kzy * 3 + kx] * sc;
-            }
-            hi[e] = rne(v);
-            lo[e] = rne(v - up(hi[e]));
-          }
-          for (int part = 0; part < 2; ++part) {
-            const unsigned* src = part ? lo : hi;
-            unsigned* dst = wb + (((size_t)chunk * 9 + kzy) * 2 + part) * 256 + lane * 4;
-            for (int q = 0; q < 4; ++q) dst[q] = src[2 * q] | (src[2 * q + 1] << 16);
-          }
-        }
+  h->c0bf_ofs = img.reserve((size_t)C0::NCH * C0::WU32);
+  pack_conv0_split(wf[0].data(), in_channels, img.words(h->c0bf_ofs));
+  h->c0f32_ofs = img.reserve((size_t)4 * 9 * 8 * 64);
+  pack_conv0_f32(wf[0].data(), in_channels, img.at(h->c0f32_ofs));
+  h->c9bf_ofs = img.reserve((size_t)C9::WU32);
+  h->c9f32_ofs = img.reserve((size_t)C9::WF32);
+  pack_conv9(wf[9].data(), img.words(h->c9bf_ofs), img.at(h->c9f32_ofs));
+  for (int l = 1; l <= 8; ++l) {
+    const int cin = kLayers[l].cin, cout = kLayers[l].cout;
+    size_t& ofs = l <= 6 ? h->cgbf_ofs[l] : h->dgbf_ofs[l - 7];
+    ofs = img.reserve((size_t)(cout / 16) * (cin / 8) * (l <= 6 ? 9 : 12) * 2 * kLoWords);
+    if (l <= 6) pack_convg(wf[l].data(), cin, cout, img.words(ofs));
+    else pack_deconvg(wf[l].data(), cin, cout, img.words(ofs));
   }
-  {
-    // exact-fp32 image of conv0 for conv0z_kernel<true> (v_mfma_f32_16x16x4_f32, pair mode): [chunk 4][kz * 3 + ky][channel 8]
-    // [lane 64]; lane (kq, m): row m = x shift * 8 + co, k = x tap kq of the 4-wide window
-    const int l = 0;
-    h->c0f32_ofs = reserve((size_t)4 * 9 * 8 * 64);
-    float* wf = host.data() + h->c0f32_ofs;
-    for (int chunk = 0; chunk < 4; ++chunk)
-      for (int kzy = 0; kzy < 9; ++kzy)
-        for (int e = 0; e < 8; ++e)
-          for (int lane = 0; lane < 64; ++lane) {
-            const int row = lane & 15, kxp = lane >> 4, sx = row >> 3, co = row & 7, kx = kxp - sx, ci = chunk * 8 + e;
-            float v = 0.f;
-            if (kx >= 0 && kx <= 2 && ci < in_channels) {
-              const float sc = bn_w[l][co] / sqrtf(bn_v[l][co] + eps);
-              v = conv_w[l][((size_t)co * in_channels + ci) * 27 + kzy * 3 + kx] * sc;
-            }
-            wf[(((size_t)chunk * 9 + kzy) * 8 + e) * 64 + lane] = v;
-          }
-  }
-  {
-    // split-bf16 image of conv9 for conv9_prob_kernel: [block 9][hi, lo][lane 64][4 words]; block = tz3 * 3 + ty3 with
-    // t?3 = {(parity 0, input 0), (0, 1), (1, 1)} <-> kernel tap {2, 0, 1}; rows = x parity * 8 + co, k = x input * 16 + ci
-    const int l = 9;
-    h->c9bf_ofs = reserve((size_t)C9::WU32);
-    unsigned* wb = reinterpret_cast<unsigned*>(host.data() + h->c9bf_ofs);
-    auto rne = [](float x) { unsigned u; memcpy(&u, &x, 4); return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16; };
-    auto up = [](unsigned hb) { unsigned u = hb << 16; float f; memcpy(&f, &u, 4); return f; };
-    static const int tap3[3] = {2, 0, 1};
-    for (int blk = 0; blk < 9; ++blk)
-      for (int lane = 0; lane < 64; ++lane) {
-        const int m = lane & 15, px = m >> 3, co = m & 7, kq = lane >> 4, dx = kq >> 1;
-        const int kz = tap3[blk / 3], ky = tap3[blk % 3];
-        const int kx = px == 0 ? (dx == 0 ? 2 : 0) : (dx == 1 ? 1 : -1);
-        const float sc = bn_w[l][co] / sqrtf(bn_v[l][co] + eps);
-        unsigned hi[8], lo[8];
-        for (int e = 0; e < 8; ++e) {
-          const int ci = (kq & 1) * 8 + e;
-          const float v = kx < 0 ? 0.f : conv_w[l][((size_t)ci * 8 + co) * 27 + kz * 9 + ky * 3 + kx] * sc;
-          hi[e] = rne(v);
-          lo[e] = rne(v - up(hi[e]));
-        }
-        for (int part = 0; part < 2; ++part) {
-          const unsigned* src = part ? lo : hi;
-          unsigned* dst = wb + ((size_t)blk * 2 + part) * 256 + lane * 4;
-          for (int q = 0; q < 4; ++q) dst[q] = src[2 * q] | (src[2 * q + 1] << 16);
-        }
-      }
-    // fp32 image of the same GEMM for conv9_prob_kernel<true>: [block 9][half 2][lane 64][4]; k slice sl = half * 4 + q of
-    // v_mfma_f32_16x16x4_f32, lane group kq: k = 4 sl + kq = x input * 16 + ci
-    h->c9f32_ofs = reserve((size_t)C9::WF32);
-    float* wf = host.data() + h->c9f32_ofs;
-    for (int blk = 0; blk < 9; ++blk)
-      for (int sl = 0; sl < 8; ++sl)
-        for (int lane = 0; lane < 64; ++lane) {
-          const int m = lane & 15, px = m >> 3, co = m & 7, kq = lane >> 4, k = 4 * sl + kq, dx = k >> 4, ci = k & 15;
-          const int kz = tap3[blk / 3], ky = tap3[blk % 3];
-          const int kx = px == 0 ? (dx == 0 ? 2 : 0) : (dx == 1 ? 1 : -1);
-          const float sc = bn_w[l][co] / sqrtf(bn_v[l][co] + eps);
-          wf[(((size_t)blk * 2 + (sl >> 2)) * 64 + lane) * 4 + (sl & 3)] =
-              kx < 0 ? 0.f : conv_w[l][((size_t)ci * 8 + co) * 27 + kz * 9 + ky * 3 + kx] * sc;
-        }
-  }
-  for (int l = 1; l <= 6; ++l) {
-    // split-bf16 images of conv1..conv6 for convg_bf16x2_kernel: [cout group][8-channel chunk][kz, ky][hi, lo][lane 64]
-    // [4 words]; rows = output channel within the group, k = 8 * x tap + ci (x tap 3 = 0)
-    static const int cins[7] = {0, 8, 16, 16, 32, 32, 64}, couts[7] = {0, 16, 16, 32, 32, 64, 64};
-    const int cin = cins[l], cout = couts[l], nch = cin / 8, ncg = cout / 16;
-    const size_t words = (size_t)ncg * nch * 9 * 2 * 64 * 4;
-    h->cgbf_ofs[l] = reserve(words);
-    unsigned* wb = reinterpret_cast<unsigned*>(host.data() + h->cgbf_ofs[l]);
-    auto rne = [](float x) { unsigned u; memcpy(&u, &x, 4); return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16; };
-    auto up = [](unsigned hb) { unsigned u = hb << 16; float f; memcpy(&f, &u, 4); return f; };
-    for (int g = 0; g < ncg; ++g)
-      for (int ch = 0; ch < nch; ++ch)
-        for (int kzy = 0; kzy < 9; ++kzy)
-          for (int lane = 0; lane < 64; ++lane) {
-            const int co = g * 16 + (lane & 15), kx = lane >> 4;
-            const float sc = bn_w[l][co] / sqrtf(bn_v[l][co] + eps);
-            unsigned hi[8], lo[8];
-            for (int e = 0; e < 8; ++e) {
-              const int ci = ch * 8 + e;
-              const float v = kx > 2 ? 0.f : conv_w[l][((size_t)co * cin + ci) * 27 + kzy * 3 + kx] * sc;
-              hi[e] = rne(v);
-              lo[e] = rne(v - up(hi[e]));
-            }
-            for (int part = 0; part < 2; ++part) {
-              const unsigned* src = part ? lo : hi;
-              unsigned* dst = wb + ((((size_t)g * nch + ch) * 9 + kzy) * 2 + part) * 256 + lane * 4;
-              for (int q = 0; q < 4; ++q) dst[q] = src[2 * q] | (src[2 * q + 1] << 16);
-            }
-          }
-  }
-  for (int l = 7; l <= 8; ++l) {
-    // split-bf16 images of conv7 / conv8 for deconvg_bf16x2_kernel: [cout group][8-channel chunk][block 12][hi, lo]
-    // [lane 64][4 words]; block = zb * 4 + (py, px), zb = {(pz 0, dz 0), (1, 0), (1, 1)}; rows = output channel,
-    // k = 8 * (dy, dx) + ci.  Kernel tap of (parity p, input d): p 0: d 0 -> 1; p 1: d 0 -> 2, d 1 -> 0.
-    const int cin = l == 7 ? 64 : 32, cout = l == 7 ? 32 : 16, nch = cin / 8, ncg = cout / 16;
-    h->dgbf_ofs[l - 7] = reserve((size_t)ncg * nch * 12 * 2 * 64 * 4);
-    unsigned* wb = reinterpret_cast<unsigned*>(host.data() + h->dgbf_ofs[l - 7]);
-    auto rne = [](float x) { unsigned u; memcpy(&u, &x, 4); return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16; };
-    auto up = [](unsigned hb) { unsigned u = hb << 16; float f; memcpy(&f, &u, 4); return f; };
-    auto tap = [](int par, int d) { return par == 0 ? (d == 0 ? 1 : -1) : (d == 0 ? 2 : 0); };
-    for (int g = 0; g < ncg; ++g)
-      for (int ch = 0; ch < nch; ++ch)
-        for (int blk = 0; blk < 12; ++blk)
-          for (int lane = 0; lane < 64; ++lane) {
-            const int zb = blk / 4, py = (blk >> 1) & 1, px = blk & 1;
-            const int pz = zb == 0 ? 0 : 1, dz = zb == 2 ? 1 : 0;
-            const int co = g * 16 + (lane & 15), dy = lane >> 5, dx = (lane >> 4) & 1;
-            const int kz = tap(pz, dz), ky = tap(py, dy), kx = tap(px, dx);
-            const float sc = bn_w[l][co] / sqrtf(bn_v[l][co] + eps);
-            unsigned hi[8], lo[8];
-            for (int e = 0; e < 8; ++e) {
-              const int ci = ch * 8 + e;
-              const float v = (kz < 0 || ky < 0 || kx < 0)
-                                  ? 0.f
-                                  : conv_w[l][((size_t)ci * cout + co) * 27 + kz * 9 + ky * 3 + kx] * sc;
-              hi[e] = rne(v);
-              lo[e] = rne(v - up(hi[e]));
-            }
-            for (int part = 0; part < 2; ++part) {
-              const unsigned* src = part ? lo : hi;
-              unsigned* dst = wb + ((((size_t)g * nch + ch) * 12 + blk) * 2 + part) * 256 + lane * 4;
-              for (int q = 0; q < 4; ++q) dst[q] = src[2 * q] | (src[2 * q + 1] << 16);
-            }
-          }
-  }
-  {
-    // prob weights for the fused kernel, channel pairs interleaved: [4 pairs][27 taps][2]
-    h->prob_w2_ofs = reserve((size_t)base * 27);
-    for (int cp = 0; cp < 4; ++cp)
-      for (int t = 0; t < 27; ++t)
-        for (int e = 0; e < 2; ++e) host[h->prob_w2_ofs + ((size_t)cp * 27 + t) * 2 + e] = prob_w[(cp * 2 + e) * 27 + t];
-  }
-  h->prob_b_ofs = reserve(1);
-  host[h->prob_b_ofs] = prob_b[0];
-  h->total = host.size();
-  hipError_t e = hipMalloc((void**)&h->dev, h->total * sizeof(float));
-  if (e != hipSuccess) { delete h; return v3d::fail(V3D_ERR_HIP, "hipMalloc(weights): %s", hipGetErrorString(e)); }
-  e = hipMemcpy(h->dev, host.data(), h->total * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void)hipFree(h->dev); delete h; return v3d::fail(V3D_ERR_HIP, "hipMemcpy(weights): %s", hipGetErrorString(e)); }
-  *out_handle = h;
-  return V3D_OK;
+  h->prob_w2_ofs = img.reserve((size_t)base * 27);
+  pack_prob(prob_w, img.at(h->prob_w2_ofs));
+  h->prob_b_ofs = img.reserve(1);
+  *img.at(h->prob_b_ofs) = prob_b[0];
+  h->total = img.data.size();
+  return v3d::finish_pack(h, img.data.data(), h->total * sizeof(float), "weights", out_handle);
 }
 
-extern "C" void v3d_costreg_free(v3d_costreg_weights* h) {
-  if (!h) return;
-  if (h->dev) (void)hipFree(h->dev);
-  delete h;
-}
+extern "C" void v3d_costreg_free(v3d_costreg_weights* h) { v3d::release(h); }
 
 static int run_layer(const v3d_costreg_weights* h, int layer, const float* in, const float* skip,
                      float* out, int n, int Di, int Hi, int Wi, int precision, hipStream_t s) {
@@ -2340,80 +2262,6 @@ extern "C" int v3d_costreg_layer_split_f32(const v3d_costreg_weights* h, int lay
     case 7: return launch_deconvg<DG<64, 32, 8, kOutF32>>("costreg_conv7", workspace, w, bias, skip, out, nullptr, n, Di, Hi, Wi, s);
     default: return launch_deconvg<DG<32, 16, 14, kOutF32>>("costreg_conv8", workspace, w, bias, skip, out, nullptr, n, Di, Hi, Wi, s);
   }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// PropagationNet (mv3d/subnetworks/upsampling.py:14-36, stage 3 of eval-3dvnet.py:101-125):
-//   x = cat(features, depth) -> 4 x [conv2d 3x3 p1 + BN + ReLU] (in -> 32 -> 32 -> 32 -> 9) -> softmax over the 9 logits
-//   -> out = sum_k p_k * depth_pad[y + k / 3, x + k % 3]   (replicate padding).
-// The whole network runs as one row-marching kernel (propz.hip: split-bf16 or exact-fp32 matrix cores, BN folded, ReLU,
-// softmax and the 3x3 propagation in the epilogue).  Nothing runs on MIOpen / PyTorch.
-// ---------------------------------------------------------------------------------------------------------------------
-struct v3d_propagation_weights {
-  int in_dim, cinp;
-  float* dev;
-  size_t zw_ofs[4], zb_ofs[4], zw32_ofs[4], total;      // split-bf16 / exact-fp32 fragment images and padded biases (propz.hip)
-};
-
-extern "C" int v3d_propagation_pack(const float* const* conv_weight_host, const float* const* bn_weight_host,
-                                    const float* const* bn_bias_host, const float* const* bn_mean_host,
-                                    const float* const* bn_var_host, int in_dim, int h_dim, float bn_eps,
-                                    v3d_propagation_weights** out_handle) {
-  V3D_REQUIRE(conv_weight_host && bn_weight_host && bn_bias_host && bn_mean_host && bn_var_host && out_handle, V3D_ERR_BAD_ARG,
-              "v3d_propagation_pack: null argument");
-  V3D_REQUIRE(h_dim == 32, V3D_ERR_UNSUPPORTED, "v3d_propagation_pack: h_dim=%d unsupported (32, lightningmodel.py:41-43)", h_dim);
-  const int cinp = (in_dim + 7) / 8 * 8;
-  V3D_REQUIRE(in_dim >= 2 && (cinp == 8 || cinp == 24 || cinp == 40), V3D_ERR_UNSUPPORTED,
-              "v3d_propagation_pack: in_dim=%d unsupported (guide channels + 1 <= 8, 17..24 or 33..40)", in_dim);
-  auto* h = new v3d_propagation_weights();
-  h->in_dim = in_dim; h->cinp = cinp; h->dev = nullptr;
-  std::vector<float> host;
-  auto reserve = [&](size_t n) { size_t o = host.size(); host.resize(o + (n + 63) / 64 * 64, 0.f); return o; };
-  // the layers for the row-marching kernel (propz.hip): K step = one tap x 32 input channels (layer 1: (tap, channel)
-  // flattened), BN scale folded, biases padded to whole 16-row blocks
-  for (int l = 0; l < 4; ++l) {
-    const int cin = l == 0 ? in_dim : 32, cout = l == 3 ? 9 : 32, op = l == 3 ? 16 : 32;
-    h->zw_ofs[l] = reserve(v3d::propz_image_words(l, cinp));
-    h->zb_ofs[l] = reserve(op);
-    h->zw32_ofs[l] = reserve(v3d::propz_image_words(l, cinp));
-    std::vector<float> wf((size_t)cout * cin * 9);
-    for (int co = 0; co < cout; ++co) {
-      const float sc = bn_weight_host[l][co] / sqrtf(bn_var_host[l][co] + bn_eps);
-      for (int i = 0; i < cin * 9; ++i) wf[(size_t)co * cin * 9 + i] = conv_weight_host[l][(size_t)co * cin * 9 + i] * sc;
-      host[h->zb_ofs[l] + co] = bn_bias_host[l][co] - bn_mean_host[l][co] * sc;
-    }
-    v3d::propz_pack_layer(l, cinp, cin, cout, wf.data(), reinterpret_cast<unsigned*>(host.data() + h->zw_ofs[l]), false);
-    v3d::propz_pack_layer(l, cinp, cin, cout, wf.data(), reinterpret_cast<unsigned*>(host.data() + h->zw32_ofs[l]), true);
-  }
-  h->total = host.size();
-  hipError_t e = hipMalloc((void**)&h->dev, h->total * sizeof(float));
-  if (e != hipSuccess) { delete h; return v3d::fail(V3D_ERR_HIP, "hipMalloc(propagation weights): %s", hipGetErrorString(e)); }
-  e = hipMemcpy(h->dev, host.data(), h->total * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void)hipFree(h->dev); delete h; return v3d::fail(V3D_ERR_HIP, "hipMemcpy(propagation weights): %s", hipGetErrorString(e)); }
-  *out_handle = h;
-  return V3D_OK;
-}
-
-extern "C" void v3d_propagation_free(v3d_propagation_weights* h) {
-  if (!h) return;
-  if (h->dev) (void)hipFree(h->dev);
-  delete h;
-}
-
-extern "C" int v3d_propagation_up_f32(const v3d_propagation_weights* h, const float* features, const float* depth_lo, int B, int Cf,
-                                      int H, int W, int h0, int w0, const int32_t* iy, const int32_t* ix, float* out, int precision,
-                                      void* stream) {
-  V3D_REQUIRE(h && features && depth_lo && out, V3D_ERR_BAD_ARG, "v3d_propagation_up_f32: null argument");
-  V3D_REQUIRE(precision == V3D_PRECISION_SPLIT_BF16 || precision == V3D_PRECISION_FP32, V3D_ERR_BAD_ARG,
-              "v3d_propagation_up_f32: unknown precision %d", precision);
-  V3D_REQUIRE(B > 0 && H > 0 && W > 0 && h0 > 0 && w0 > 0 && Cf + 1 == h->in_dim, V3D_ERR_BAD_SHAPE,
-              "v3d_propagation_up_f32: bad shape (B=%d, Cf=%d, H=%d, W=%d, depth %d x %d; packed for in_dim=%d)", B, Cf, H, W, h0, w0, h->in_dim);
-  V3D_REQUIRE((iy && ix) || (!iy && !ix && h0 == H && w0 == W), V3D_ERR_BAD_ARG,
-              "v3d_propagation_up_f32: both index tables, or none with a depth of the output size");
-  const bool f32 = precision == V3D_PRECISION_FP32;
-  const float* w[4]; const float* b[4];
-  for (int l = 0; l < 4; ++l) { w[l] = h->dev + (f32 ? h->zw32_ofs[l] : h->zw_ofs[l]); b[l] = h->dev + h->zb_ofs[l]; }
-  return v3d::launch_propz(h->cinp, f32, features, depth_lo, iy, ix, out, w, b, B, Cf, H, W, h0, w0, (hipStream_t)stream);
 }
 
 namespace {

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "v3d_common.h"
+#include "weight_pack.h"
 
 struct v3d_fpn_weights {
   int cin, csteps;
@@ -213,18 +214,6 @@ __global__ __launch_bounds__(256, 2) void fpn_level_kernel(FpnParams p) {
   }
 }
 
-unsigned fpn_rne(float x) {
-  unsigned u;
-  memcpy(&u, &x, 4);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-float fpn_bf16_value(unsigned h) {
-  const unsigned u = h << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-
 }  // namespace
 
 // HOST weights: w_lateral [32, cin] (+ b_lateral [32]), w_out [32, 32, 3, 3] (+ b_out [32]); cin a multiple of 8, <= 48
@@ -238,8 +227,8 @@ extern "C" int v3d_fpn_pack(const float* w_lateral, const float* b_lateral, cons
   h->bias_ofs = h->w3_ofs + kW3Bytes;
   std::vector<unsigned char> host(h->bias_ofs + 64 * 4, 0);
   auto put = [&](size_t hi_ofs, float w) {
-    const unsigned hi = fpn_rne(w), lo = fpn_rne(w - fpn_bf16_value(hi));
-    const unsigned short h16 = (unsigned short)hi, l16 = (unsigned short)lo;
+    unsigned short h16, l16;
+    v3d::split_bf16(w, h16, l16);
     memcpy(&host[hi_ofs], &h16, 2);
     memcpy(&host[hi_ofs + 1024], &l16, 2);
   };
@@ -258,19 +247,10 @@ extern "C" int v3d_fpn_pack(const float* w_lateral, const float* b_lateral, cons
         }
   float* const bias = reinterpret_cast<float*>(&host[h->bias_ofs]);
   for (int c = 0; c < 32; ++c) { bias[c] = b_lateral[c]; bias[32 + c] = b_out[c]; }
-  hipError_t e = hipMalloc((void**)&h->dev, host.size());
-  if (e != hipSuccess) { delete h; return v3d::fail(V3D_ERR_HIP, "hipMalloc(pyramid weights): %s", hipGetErrorString(e)); }
-  e = hipMemcpy(h->dev, host.data(), host.size(), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void)hipFree(h->dev); delete h; return v3d::fail(V3D_ERR_HIP, "hipMemcpy(pyramid weights): %s", hipGetErrorString(e)); }
-  *out_handle = h;
-  return V3D_OK;
+  return v3d::finish_pack(h, host.data(), host.size(), "pyramid weights", out_handle);
 }
 
-extern "C" void v3d_fpn_free(v3d_fpn_weights* h) {
-  if (!h) return;
-  if (h->dev) (void)hipFree(h->dev);
-  delete h;
-}
+extern "C" void v3d_fpn_free(v3d_fpn_weights* h) { v3d::release(h); }
 
 // x [n, H, W, cin] channels-last; coarse_inner [n, ceil(H/2), ceil(W/2), 32] channels-last or NULL (the coarsest level);
 // inner_out [n, H, W, 32] channels-last or NULL (the finest level: nobody reads it); out [n, 32, H, W] (the reference layout)
@@ -293,14 +273,8 @@ extern "C" int v3d_fpn_level_f32(const v3d_fpn_weights* h, const float* x, const
   hipStream_t s = (hipStream_t)stream;
   const int lds = kWL + h->csteps * 2048;
   void (*kernel)(FpnParams) = h->csteps == 1 ? fpn_level_kernel<1> : h->csteps == 2 ? fpn_level_kernel<2> : fpn_level_kernel<3>;
-  static bool attr_set[64][3] = {};
-  int dev = 0;
-  V3D_CHECK_HIP(hipGetDevice(&dev));
-  V3D_REQUIRE(dev >= 0 && dev < 64, V3D_ERR_UNSUPPORTED, "device ordinal %d", dev);
-  if (!attr_set[dev][h->csteps - 1]) {
-    V3D_CHECK_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    attr_set[dev][h->csteps - 1] = true;
-  }
+  static bool lds_opted[3][64] = {};
+  if (const int rc = v3d::opt_in_dynamic_lds((const void*)kernel, lds, lds_opted[h->csteps - 1]); rc != V3D_OK) return rc;
   const unsigned grid = v3d::persistent_grid(tiles, 2);
   v3d::TimedScope ts("backbone_pyramid_level", s);
   kernel<<<grid, 256, lds, s>>>(p);

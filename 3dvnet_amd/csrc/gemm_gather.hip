@@ -24,6 +24,7 @@
 
 #include "v3d_common.h"
 #include "gemm_weights.h"
+#include "weight_pack.h"
 
 namespace {
 
@@ -976,19 +977,22 @@ extern "C" int v3d_gemm_pack(const float* w_host, long long stride_seg, long lon
   const int MB = 4 * h->MBW, nkc = h->KP / kKC;
   const size_t wslab = (size_t)MB * 16 * kKC;
   std::vector<float> host((size_t)n_seg * nkc * wslab + 3 * 128, 0.f);   // grown below for the bf16 image
+  // weight (segment s, output co, k) with the per-output scale folded; 0 in the padding of N and K
+  auto weight = [&](int s, int co, int k) {
+    float v = 0.f;
+    if (co < N && k < K) {
+      v = w_host[s * stride_seg + co * stride_co + k * stride_k];
+      if (scale_host) v *= scale_host[co];
+    }
+    return v;
+  };
   for (int s = 0; s < n_seg; ++s)
     for (int kc = 0; kc < nkc; ++kc)
       for (int k4 = 0; k4 < kKC / 4; ++k4)
         for (int mb = 0; mb < MB; ++mb)
-          for (int lane = 0; lane < 64; ++lane) {
-            const int co = mb * 16 + (lane & 15), k = kc * kKC + k4 * 4 + (lane >> 4);
-            float v = 0.f;
-            if (co < N && k < K) {
-              v = w_host[s * stride_seg + co * stride_co + k * stride_k];
-              if (scale_host) v *= scale_host[co];
-            }
-            host[((size_t)(s * nkc + kc) * wslab) + ((size_t)(k4 * MB + mb) * 64) + lane] = v;
-          }
+          for (int lane = 0; lane < 64; ++lane)
+            host[((size_t)(s * nkc + kc) * wslab) + ((size_t)(k4 * MB + mb) * 64) + lane] =
+                weight(s, mb * 16 + (lane & 15), kc * kKC + k4 * 4 + (lane >> 4));
   h->bias_ofs = (size_t)n_seg * nkc * wslab;
   h->gnw_ofs = h->bias_ofs + 128;
   h->gnb_ofs = h->gnw_ofs + 128;
@@ -998,56 +1002,32 @@ extern "C" int v3d_gemm_pack(const float* w_host, long long stride_seg, long lon
   host.resize(h->bf_ofs + (size_t)n_seg * nkc * wslab, 0.f);
   {
     unsigned* wb = reinterpret_cast<unsigned*>(host.data() + h->bf_ofs);
-    auto rne = [](float x) { unsigned u; memcpy(&u, &x, 4); return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16; };
-    auto up = [](unsigned hb) { unsigned u = hb << 16; float f; memcpy(&f, &u, 4); return f; };
     for (int s = 0; s < n_seg; ++s)
       for (int kc = 0; kc < nkc; ++kc)
         for (int mb = 0; mb < MB; ++mb)
           for (int lane = 0; lane < 64; ++lane) {
-            unsigned hi[8], lo[8];
-            for (int e = 0; e < 8; ++e) {
-              const int co = mb * 16 + (lane & 15), k = kc * kKC + 8 * (lane >> 4) + e;
-              float v = 0.f;
-              if (co < N && k < K) {
-                v = w_host[s * stride_seg + co * stride_co + k * stride_k];
-                if (scale_host) v *= scale_host[co];
-              }
-              hi[e] = rne(v);
-              lo[e] = rne(v - up(hi[e]));
-            }
-            for (int part = 0; part < 2; ++part) {
-              const unsigned* src = part ? lo : hi;
-              unsigned* dst = wb + (size_t)(s * nkc + kc) * wslab + ((size_t)(part * MB + mb) * 64 + lane) * 4;
-              for (int q = 0; q < 4; ++q) dst[q] = src[2 * q] | (src[2 * q + 1] << 16);
-            }
+            float v[8];
+            for (int e = 0; e < 8; ++e) v[e] = weight(s, mb * 16 + (lane & 15), kc * kKC + 8 * (lane >> 4) + e);
+            unsigned* dst = wb + (size_t)(s * nkc + kc) * wslab + ((size_t)mb * 64 + lane) * 4;
+            v3d::split_bf16x8(v, dst, dst + (size_t)MB * 256);
           }
   }
+  // the fused hypothesis decoder's image (gemm_weights.h, dec_ofs)
   h->dec_ofs = 0;
   if (n_seg == 3 && N == 128 && K % 16 == 0) {
     const int nst = K / 16;
     h->dec_ofs = host.size();
     host.resize(h->dec_ofs + (size_t)nst * 24 * 256, 0.f);
     unsigned* wb = reinterpret_cast<unsigned*>(host.data() + h->dec_ofs);
-    auto rne = [](float x) { unsigned u; memcpy(&u, &x, 4); return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16; };
-    auto up = [](unsigned hb) { unsigned u = hb << 16; float f; memcpy(&f, &u, 4); return f; };
     for (int st = 0; st < nst; ++st)
       for (int t = 0; t < 3; ++t)
         for (int mb = 0; mb < 4; ++mb)
           for (int lane = 0; lane < 64; ++lane) {
-            unsigned hi[8], lo[8];
             const int co = mb * 32 + (lane & 31), g = lane >> 5;
-            for (int e = 0; e < 8; ++e) {
-              const int k = 16 * st + 8 * (e >> 2) + 4 * g + (e & 3);
-              float v = w_host[t * stride_seg + co * stride_co + k * stride_k];
-              if (scale_host) v *= scale_host[co];
-              hi[e] = rne(v);
-              lo[e] = rne(v - up(hi[e]));
-            }
-            for (int part = 0; part < 2; ++part) {
-              const unsigned* src = part ? lo : hi;
-              unsigned* dst = wb + ((((size_t)st * 3 + t) * 2 + part) * 4 + mb) * 256 + (size_t)lane * 4;
-              for (int q = 0; q < 4; ++q) dst[q] = src[2 * q] | (src[2 * q + 1] << 16);
-            }
+            float v[8];
+            for (int e = 0; e < 8; ++e) v[e] = weight(t, co, 16 * st + 8 * (e >> 2) + 4 * g + (e & 3));
+            unsigned* dst = wb + ((((size_t)st * 3 + t) * 2) * 4 + mb) * 256 + (size_t)lane * 4;
+            v3d::split_bf16x8(v, dst, dst + 4 * 256);
           }
   }
   h->has_bias = bias_host != nullptr;
@@ -1056,19 +1036,10 @@ extern "C" int v3d_gemm_pack(const float* w_host, long long stride_seg, long lon
     if (bias_host) host[h->bias_ofs + i] = bias_host[i];
     if (h->has_gn) { host[h->gnw_ofs + i] = gn_w_host[i]; host[h->gnb_ofs + i] = gn_b_host[i]; }
   }
-  hipError_t e = hipMalloc((void**)&h->dev, host.size() * sizeof(float));
-  if (e != hipSuccess) { delete h; return v3d::fail(V3D_ERR_HIP, "hipMalloc(gemm weights): %s", hipGetErrorString(e)); }
-  e = hipMemcpy(h->dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void)hipFree(h->dev); delete h; return v3d::fail(V3D_ERR_HIP, "hipMemcpy(gemm weights): %s", hipGetErrorString(e)); }
-  *out_handle = h;
-  return V3D_OK;
+  return v3d::finish_pack(h, host.data(), host.size() * sizeof(float), "gemm weights", out_handle);
 }
 
-extern "C" void v3d_gemm_free(v3d_gemm_weights* h) {
-  if (!h) return;
-  if (h->dev) (void)hipFree(h->dev);
-  delete h;
-}
+extern "C" void v3d_gemm_free(v3d_gemm_weights* h) { v3d::release(h); }
 
 extern "C" int v3d_gemm_gather_f32(const v3d_gemm_weights* h, int M, const float* const* seg_src_host,
                                    const int32_t* const* seg_idx_host, const int* seg_ld_host,

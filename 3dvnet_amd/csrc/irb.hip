@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "v3d_common.h"
+#include "weight_pack.h"
 
 struct v3d_irb_weights {
   int cin, mid, cout, ks, stride, residual, stem;
@@ -428,18 +429,6 @@ __global__ __launch_bounds__(256) void irb_reduce_kernel(const float* __restrict
   *reinterpret_cast<f32x4*>(out + k) = v;
 }
 
-unsigned irb_rne(float x) {
-  unsigned u;
-  memcpy(&u, &x, 4);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-float irb_bf16_value(unsigned h) {
-  const unsigned u = h << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-
 // the instantiations the MnasNet-1.0 trunk needs at image sides that are multiples of 32 (and at 240 x 320); anything else takes
 // the three-launch path
 struct IrbVariant {
@@ -505,8 +494,8 @@ int irb_pack_impl(const float* w_expand, const float* b_expand, const float* w_d
   h->bp_ofs = h->pw_ofs + h->pw_slice * h->ns;
   std::vector<unsigned char> host(h->bp_ofs + (size_t)h->ncbo * 32 * 4, 0);
   auto put_bf16 = [&](size_t byte_ofs_hi, size_t byte_ofs_lo, float w) {
-    const unsigned hi = irb_rne(w), lo = irb_rne(w - irb_bf16_value(hi));
-    const unsigned short h16 = (unsigned short)hi, l16 = (unsigned short)lo;
+    unsigned short h16, l16;
+    v3d::split_bf16(w, h16, l16);
     memcpy(&host[byte_ofs_hi], &h16, 2);
     memcpy(&host[byte_ofs_lo], &l16, 2);
   };
@@ -541,12 +530,7 @@ int irb_pack_impl(const float* w_expand, const float* b_expand, const float* w_d
   }
   float* const bp = reinterpret_cast<float*>(&host[h->bp_ofs]);
   for (int co = 0; co < cout; ++co) bp[co] = b_project[co];
-  hipError_t e = hipMalloc((void**)&h->dev, host.size());
-  if (e != hipSuccess) { delete h; return v3d::fail(V3D_ERR_HIP, "hipMalloc(block weights): %s", hipGetErrorString(e)); }
-  e = hipMemcpy(h->dev, host.data(), host.size(), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void)hipFree(h->dev); delete h; return v3d::fail(V3D_ERR_HIP, "hipMemcpy(block weights): %s", hipGetErrorString(e)); }
-  *out_handle = h;
-  return V3D_OK;
+  return v3d::finish_pack(h, host.data(), host.size(), "block weights", out_handle);
 }
 }  // namespace
 
@@ -579,11 +563,7 @@ extern "C" int v3d_stem_block_f32(const v3d_irb_weights* h, const float* image, 
   return v3d_irb_launch(h, image, n, IH / 2, IW / 2, IH, IW, out, nullptr, 0, stream);
 }
 
-extern "C" void v3d_irb_free(v3d_irb_weights* h) {
-  if (!h) return;
-  if (h->dev) (void)hipFree(h->dev);
-  delete h;
-}
+extern "C" void v3d_irb_free(v3d_irb_weights* h) { v3d::release(h); }
 
 #ifdef V3D_IRB_PHASE
 extern "C" int v3d_debug_irb_phase(unsigned long long* out8, int reset) {
@@ -654,15 +634,8 @@ int v3d_irb_launch(const v3d_irb_weights* h, const float* x, int n, int H, int W
   V3D_REQUIRE(blocks < (1ll << 31) && (long long)n * H * W * (h->cin > h->cout ? h->cin : h->cout) < (1ll << 40), V3D_ERR_BAD_SHAPE,
               "v3d_irb_nhwc_f32: %lld tiles", blocks);
   hipStream_t s = (hipStream_t)stream;
-  static bool attr_set[64][sizeof(kIrbVariants) / sizeof(kIrbVariants[0])] = {};
-  int dev = 0;
-  V3D_CHECK_HIP(hipGetDevice(&dev));
-  V3D_REQUIRE(dev >= 0 && dev < 64, V3D_ERR_UNSUPPORTED, "device ordinal %d", dev);
-  const int vi = (int)(v - kIrbVariants);
-  if (!attr_set[dev][vi]) {
-    V3D_CHECK_HIP(hipFuncSetAttribute((const void*)v->kernel, hipFuncAttributeMaxDynamicSharedMemorySize, v->lds));
-    attr_set[dev][vi] = true;
-  }
+  static bool lds_opted[sizeof(kIrbVariants) / sizeof(kIrbVariants[0])][64] = {};
+  if (const int rc = v3d::opt_in_dynamic_lds((const void*)v->kernel, v->lds, lds_opted[v - kIrbVariants]); rc != V3D_OK) return rc;
   v3d::TimedScope ts(h->stem ? "backbone_stem_block" : "backbone_block", s);
   v->kernel<<<(unsigned)blocks, 256, v->lds, s>>>(p);
   V3D_CHECK_LAUNCH("irb_kernel");

@@ -19,10 +19,14 @@
 // Columns: a strip computes 48 columns (3 MFMA column blocks of 16) for 40 outputs -- every layer loses one column per side.
 // A ring row is stored as planes of 16-byte chunks (kPLS below: conflict-free B-fragment reads).  Zero padding of every convolution: image-border columns / rows are written as zeros by the producing
 // wave (not as "the convolution evaluated outside the image").
+//
+// The host side is at the bottom of the file: the fragment images of the four layers, the launch, and the C ABI
+// (v3d_propagation_pack / _free / _up_f32).
 #include <cstring>
 #include <mutex>
 
 #include "v3d_common.h"
+#include "weight_pack.h"
 
 namespace {
 
@@ -437,14 +441,8 @@ __global__ __launch_bounds__(kThreads, 2) void propz_kernel(PropzParams p) {
 
 template <int G, bool F32>
 int launch_g(const PropzParams& p, hipStream_t s) {
-  static bool attr_set[64] = {false};      // per device: the dynamic-LDS opt-in is a per-device function attribute
-  int dev = 0;
-  V3D_CHECK_HIP(hipGetDevice(&dev));
-  V3D_REQUIRE(dev >= 0 && dev < 64, V3D_ERR_UNSUPPORTED, "device ordinal %d", dev);
-  if (!attr_set[dev]) {
-    V3D_CHECK_HIP(hipFuncSetAttribute((const void*)propz_kernel<G, F32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PZ<G>::LDS));
-    attr_set[dev] = true;
-  }
+  static bool lds_opted[64] = {};
+  if (const int rc = v3d::opt_in_dynamic_lds((const void*)propz_kernel<G, F32>, (int)PZ<G>::LDS, lds_opted); rc != V3D_OK) return rc;
   const long long items = (long long)p.B * p.nstrip;
   const unsigned grid = v3d::persistent_grid(items, 1);
   {
@@ -455,46 +453,43 @@ int launch_g(const PropzParams& p, hipStream_t s) {
   return V3D_OK;
 }
 
-}  // namespace
-
-// Host side of the fragment images (v3d_propagation_pack, costreg.hip): words of layer l in the order the kernel reads them.
+// Host side of the fragment images (v3d_propagation_pack below): words of layer l in the order the kernel reads them.
 //   K step ks, 16-row block cb, part (hi, lo), lane (kq = lane >> 4, m = lane & 15): row = output channel cb * 16 + m, the lane's
 //   8 k values e = 0 .. 7:  layers 2..4: tap = ks, input channel = 8 kq + e;  layer 1: k8 = ks * 4 + kq, tap = k8 / G (zero
 //   weights for tap >= 9), input channel = (k8 % G) * 8 + e.
-size_t v3d::propz_image_words(int layer, int cinp) {
+size_t propz_image_words(int layer, int cinp) {
   const int G = cinp / 8, ks = layer == 0 ? (9 * G + 3) / 4 : 9, ncb = layer == 3 ? 1 : 2;
   return (size_t)ks * ncb * 2 * 64 * 4;
 }
 
-void v3d::propz_pack_layer(int layer, int cinp, int cin, int cout, const float* w_folded, unsigned* out, bool f32) {
+// `w_folded` = BN-folded weights [cout][cin][3][3]; `cinp` = padded input channels of layer 0 (8 | 24 | 40)
+void propz_pack_layer(int layer, int cinp, int cin, int cout, const float* w_folded, unsigned* out, bool f32) {
   const int G = cinp / 8, KS = layer == 0 ? (9 * G + 3) / 4 : 9, ncb = layer == 3 ? 1 : 2;
-  auto rne = [](float x) { unsigned u; memcpy(&u, &x, 4); return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16; };
-  auto up = [](unsigned hb) { unsigned u = hb << 16; float f; memcpy(&f, &u, 4); return f; };
   for (int ks = 0; ks < KS; ++ks)
     for (int cb = 0; cb < ncb; ++cb)
       for (int lane = 0; lane < 64; ++lane) {
         const int kq = lane >> 4, co = cb * 16 + (lane & 15);
-        unsigned hi[8], lo[8];
+        float v[8];
         for (int e = 0; e < 8; ++e) {
           int tap, ci;
           if (layer == 0) { const int k8 = ks * 4 + kq; tap = k8 / G; ci = (k8 % G) * 8 + e; }
           else { tap = ks; ci = 8 * kq + e; }
-          float v = 0.f;
-          if (tap < 9 && co < cout && ci < cin) v = w_folded[((size_t)co * cin + ci) * 9 + tap];      // [cout][cin][ky][kx]
-          hi[e] = rne(v);
-          lo[e] = rne(v - up(hi[e]));
-          if (f32) memcpy(&hi[e], &v, 4);      // exact-fp32 image: part 0 = k slices 0..3, part 1 = 4..7 (slice e <-> channel 8 kq + e)
+          v[e] = tap < 9 && co < cout && ci < cin ? w_folded[((size_t)co * cin + ci) * 9 + tap] : 0.f;      // [cout][cin][ky][kx]
         }
-        for (int part = 0; part < 2; ++part) {
-          const unsigned* src = part ? lo : hi;
-          unsigned* dst = out + ((((size_t)ks * ncb + cb) * 2 + part) * 64 + lane) * 4;
-          for (int q = 0; q < 4; ++q) dst[q] = f32 ? hi[4 * part + q] : (src[2 * q] | (src[2 * q + 1] << 16));
+        unsigned* dst = out + ((((size_t)ks * ncb + cb) * 2) * 64 + lane) * 4;
+        if (f32) {      // exact-fp32 image: part 0 = k slices 0..3, part 1 = 4..7 (slice e <-> channel 8 kq + e)
+          memcpy(dst, v, 16);
+          memcpy(dst + 256, v + 4, 16);
+        } else {
+          v3d::split_bf16x8(v, dst, dst + 256);
         }
       }
 }
 
-int v3d::launch_propz(int cinp, bool f32, const float* feat, const float* depth, const int* iy, const int* ix, float* out,
-                      const float* const w[4], const float* const bias[4], int B, int Cf, int H, int W, int h0, int w0, hipStream_t s) {
+// `depth` is [B, h0, w0]; with index tables iy [H] / ix [W] (device, may be null = identity with h0 == H, w0 == W) the
+// nearest-neighbour resize of the depth (eval-3dvnet.py:103,111,119) happens in the kernel's addressing.
+int launch_propz(int cinp, bool f32, const float* feat, const float* depth, const int* iy, const int* ix, float* out,
+                 const float* const w[4], const float* const bias[4], int B, int Cf, int H, int W, int h0, int w0, hipStream_t s) {
   PropzParams p;
   p.feat = feat; p.depth = depth; p.iy = iy; p.ix = ix; p.out = out;
   for (int l = 0; l < 4; ++l) { p.w[l] = reinterpret_cast<const u32x4*>(w[l]); p.bias[l] = bias[l]; }
@@ -505,4 +500,67 @@ int v3d::launch_propz(int cinp, bool f32, const float* feat, const float* depth,
   if (cinp == 24) return f32 ? launch_g<3, true>(p, s) : launch_g<3, false>(p, s);
   if (cinp == 40) return f32 ? launch_g<5, true>(p, s) : launch_g<5, false>(p, s);
   return v3d::fail(V3D_ERR_UNSUPPORTED, "propagation: %d padded input channels (8, 24, 40)", cinp);
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------
+// PropagationNet (mv3d/subnetworks/upsampling.py:14-36, stage 3 of eval-3dvnet.py:101-125):
+//   x = cat(features, depth) -> 4 x [conv2d 3x3 p1 + BN + ReLU] (in -> 32 -> 32 -> 32 -> 9) -> softmax over the 9 logits
+//   -> out = sum_k p_k * depth_pad[y + k / 3, x + k % 3]   (replicate padding).
+// The whole network runs as one row-marching kernel (above: split-bf16 or exact-fp32 matrix cores, BN folded, ReLU,
+// softmax and the 3x3 propagation in the epilogue).  Nothing runs on MIOpen / PyTorch.
+// ---------------------------------------------------------------------------------------------------------------------
+struct v3d_propagation_weights {
+  int in_dim, cinp;
+  float* dev;
+  size_t zw_ofs[4], zb_ofs[4], zw32_ofs[4], total;      // split-bf16 / exact-fp32 fragment images and padded biases
+};
+
+extern "C" int v3d_propagation_pack(const float* const* conv_weight_host, const float* const* bn_weight_host,
+                                    const float* const* bn_bias_host, const float* const* bn_mean_host,
+                                    const float* const* bn_var_host, int in_dim, int h_dim, float bn_eps,
+                                    v3d_propagation_weights** out_handle) {
+  V3D_REQUIRE(conv_weight_host && bn_weight_host && bn_bias_host && bn_mean_host && bn_var_host && out_handle, V3D_ERR_BAD_ARG,
+              "v3d_propagation_pack: null argument");
+  V3D_REQUIRE(h_dim == 32, V3D_ERR_UNSUPPORTED, "v3d_propagation_pack: h_dim=%d unsupported (32, lightningmodel.py:41-43)", h_dim);
+  const int cinp = (in_dim + 7) / 8 * 8;
+  V3D_REQUIRE(in_dim >= 2 && (cinp == 8 || cinp == 24 || cinp == 40), V3D_ERR_UNSUPPORTED,
+              "v3d_propagation_pack: in_dim=%d unsupported (guide channels + 1 <= 8, 17..24 or 33..40)", in_dim);
+  auto* h = new v3d_propagation_weights();
+  h->in_dim = in_dim; h->cinp = cinp; h->dev = nullptr;
+  v3d::HostImage img;
+  // the layers for the row-marching kernel: K step = one tap x 32 input channels (layer 1: (tap, channel) flattened), BN scale
+  // folded, biases padded to whole 16-row blocks
+  for (int l = 0; l < 4; ++l) {
+    const int cin = l == 0 ? in_dim : 32, cout = l == 3 ? 9 : 32, op = l == 3 ? 16 : 32;
+    h->zw_ofs[l] = img.reserve(propz_image_words(l, cinp));
+    h->zb_ofs[l] = img.reserve(op);
+    h->zw32_ofs[l] = img.reserve(propz_image_words(l, cinp));
+    const v3d::BnFold bn(bn_weight_host[l], bn_bias_host[l], bn_mean_host[l], bn_var_host[l], bn_eps, cout);
+    const std::vector<float> wf = bn.weights(conv_weight_host[l], 1, (size_t)cin * 9);
+    memcpy(img.at(h->zb_ofs[l]), bn.bias.data(), cout * sizeof(float));
+    propz_pack_layer(l, cinp, cin, cout, wf.data(), img.words(h->zw_ofs[l]), false);
+    propz_pack_layer(l, cinp, cin, cout, wf.data(), img.words(h->zw32_ofs[l]), true);
+  }
+  h->total = img.data.size();
+  return v3d::finish_pack(h, img.data.data(), h->total * sizeof(float), "propagation weights", out_handle);
+}
+
+extern "C" void v3d_propagation_free(v3d_propagation_weights* h) { v3d::release(h); }
+
+extern "C" int v3d_propagation_up_f32(const v3d_propagation_weights* h, const float* features, const float* depth_lo, int B, int Cf,
+                                      int H, int W, int h0, int w0, const int32_t* iy, const int32_t* ix, float* out, int precision,
+                                      void* stream) {
+  V3D_REQUIRE(h && features && depth_lo && out, V3D_ERR_BAD_ARG, "v3d_propagation_up_f32: null argument");
+  V3D_REQUIRE(precision == V3D_PRECISION_SPLIT_BF16 || precision == V3D_PRECISION_FP32, V3D_ERR_BAD_ARG,
+              "v3d_propagation_up_f32: unknown precision %d", precision);
+  V3D_REQUIRE(B > 0 && H > 0 && W > 0 && h0 > 0 && w0 > 0 && Cf + 1 == h->in_dim, V3D_ERR_BAD_SHAPE,
+              "v3d_propagation_up_f32: bad shape (B=%d, Cf=%d, H=%d, W=%d, depth %d x %d; packed for in_dim=%d)", B, Cf, H, W, h0, w0, h->in_dim);
+  V3D_REQUIRE((iy && ix) || (!iy && !ix && h0 == H && w0 == W), V3D_ERR_BAD_ARG,
+              "v3d_propagation_up_f32: both index tables, or none with a depth of the output size");
+  const bool f32 = precision == V3D_PRECISION_FP32;
+  const float* w[4]; const float* b[4];
+  for (int l = 0; l < 4; ++l) { w[l] = h->dev + (f32 ? h->zw32_ofs[l] : h->zw_ofs[l]); b[l] = h->dev + h->zb_ofs[l]; }
+  return launch_propz(h->cinp, f32, features, depth_lo, iy, ix, out, w, b, B, Cf, H, W, h0, w0, (hipStream_t)stream);
 }

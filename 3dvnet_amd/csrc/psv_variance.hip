@@ -21,6 +21,7 @@
 
 #include <vector>
 
+#include "bf16_split.h"
 #include "v3d_common.h"
 
 namespace {
@@ -204,17 +205,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ unsigned psv_bf16_rne(float x) {
-  unsigned u = __float_as_uint(x);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-
-// two fp32 -> two bf16 (round to nearest even) packed in one dword, a in the low half: one v_cvt_pk_bf16_f32
-typedef __bf16 psv_bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
-  typedef float f32x2_ __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_){a, b}, psv_bf16x2));
-}
+using v3d::bf16_rne;      // bf16_split.h
+using v3d::pack_bf16x2;
 
 // One wave per workgroup (16 pixels x 4 planes).  The projection, gather and store phases of a workgroup are separated
 // by barriers; with single-wave workgroups the barriers are free and the 24 resident waves of a CU drift apart, so the L1
@@ -354,8 +346,8 @@ __global__ __launch_bounds__(64) void psv_variance_kernel(PsvParams p) {
           const float avg = acc_s[a][k] / cnt;
           const float avg_sq = acc_q[a][k] / cnt;
           const float v = v3d::sub_rn(avg_sq, v3d::mul_rn(avg, avg));            // mvsnet.py:216
-          h[k] = psv_bf16_rne(v);
-          l[k] = psv_bf16_rne(v - __uint_as_float(h[k] << 16));
+          h[k] = bf16_rne(v);
+          l[k] = bf16_rne(v - __uint_as_float(h[k] << 16));
         }
         s_sp[(((chunk * 2 + 0) * (kPix + 1)) + px) * 2 + half] = (u32x2){h[0] | (h[1] << 16), h[2] | (h[3] << 16)};
         s_sp[(((chunk * 2 + 1) * (kPix + 1)) + px) * 2 + half] = (u32x2){l[0] | (l[1] << 16), l[2] | (l[3] << 16)};

@@ -78,6 +78,19 @@ inline unsigned persistent_grid(long long n_tiles, int wgs_per_cu) {
   return (unsigned)g;
 }
 
+// A kernel that needs more dynamic LDS than the 64 KB default opts in once per device (the attribute is per device and per
+// function): `done_per_device` is the kernel's (instantiation's) own static row of 64 flags.
+inline int opt_in_dynamic_lds(const void* kernel, int bytes, bool* done_per_device) {
+  int dev = 0;
+  V3D_CHECK_HIP(hipGetDevice(&dev));
+  V3D_REQUIRE(dev >= 0 && dev < 64, V3D_ERR_UNSUPPORTED, "device ordinal %d", dev);
+  if (!done_per_device[dev]) {
+    V3D_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    done_per_device[dev] = true;
+  }
+  return V3D_OK;
+}
+
 struct TimedScope {
   hipStream_t s;
   bool on;
@@ -225,15 +238,6 @@ int launch_conv0z(bool f32, const void* in, const float* wimg, const float* bias
 // -> conv2 output [n][2 groups][hi, lo][D2][H2][W2]; `w1` / `w2` = the split-bf16 images of conv1 / conv2 (costreg.hip, cgbf)
 int launch_conv12z(const void* c0_split, const float* w1, const float* w2, const float* b1, const float* b2, void* out_split,
                    int n, int D, int H, int W, hipStream_t s);
-
-// PropagationNet as one row-marching kernel (propz.hip, round 6): the fragment images of a layer (layer 0..3; `cinp` = padded input
-// channels of layer 0: 8 | 24 | 40) packed from BN-folded weights [cout][cin][3][3], and the launch.  `depth` is [B, h0, w0]; with
-// index tables iy [H] / ix [W] (device, may be null = identity with h0 == H, w0 == W) the nearest-neighbour resize of the depth
-// (eval-3dvnet.py:103,111,119) happens in the kernel's addressing.
-size_t propz_image_words(int layer, int cinp);
-void propz_pack_layer(int layer, int cinp, int cin, int cout, const float* w_folded, unsigned* out, bool f32);
-int launch_propz(int cinp, bool f32, const float* feat, const float* depth, const int* iy, const int* ix, float* out,
-                 const float* const w[4], const float* const bias[4], int B, int Cf, int H, int W, int h0, int w0, hipStream_t s);
 
 // [n_img, C, HW] -> [n_img, HW, C] (C in {16, 32}); defined in psv_variance.hip
 int transpose_channel_last(const float* feat, float* featT, int n_img, int C, int HW, hipStream_t s);

@@ -80,6 +80,9 @@ def build(force=False, verbose=False, strict=False):
             isa_check.check_no_scratch(os.path.join(objdir, 'cloudmetrics.o'), 'nn_query_kernel', strict=strict)
             # mesh extraction: the status bytes of a cell, its table row and the vertex state stay in registers
             isa_check.check_no_scratch(os.path.join(objdir, 'mesh.o'), 'mc_[a-z_]*_kernel', strict=strict)
+            # plane-sweep warp: the window kernel walks the depth axis at the register limit of 4 waves per SIMD; what it keeps
+            # across the walk must stay in registers
+            isa_check.check_no_scratch(os.path.join(objdir, 'psv_variance.o'), 'psv_variance_window_kernel', strict=strict)
         finally:
             sys.path.pop(0)
     if force or procs or linked != tag or _stale(LIB, objs):

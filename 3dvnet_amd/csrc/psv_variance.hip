@@ -46,7 +46,10 @@ struct PsvParams {
   // window kernel: launch constants the host works out once -- per wave they were two IEEE f64 divisions and three integer
   // divisions through v_rcp_iflag_f32 (round 4: ~110 of the ~2 100 VALU issue slots of a wave at cfg2)
   float rWm1, rHm1;                        // (float)(1.0 / (double)(W - 1)), (float)(1.0 / (double)(H - 1))
-  unsigned m_dchunk, m_ptile, m_w;         // v3d::magic_u32() of the plane-chunk count, of n_ptile and of w (0: divide)
+  unsigned m_dseg, m_ptile, m_w;           // v3d::magic_u32() of n_dseg, of n_ptile and of w (0: divide)
+  // window kernel, depth walk: a wave owns its 8 pixels for `walk` consecutive chunks of kRDB planes (one depth segment; the
+  // last segment of a volume may be shorter)
+  int n_dchunk, walk, n_dseg;              // plane chunks per volume, chunks per segment, segments per volume
 };
 
 
@@ -666,7 +669,10 @@ __device__ __forceinline__ int psv_smax(int a, int b) { int r; asm("s_max_i32 %0
 // CL8 (with SPLIT's geometry: one wave per workgroup, direct stores): the volume leaves as fp32 in the channel-last layout
 // of the exact-fp32 depth-march conv0 (conv0z.hip) -- [n_ref][4 channel groups][2 halves][D][h][w] 16-byte slots of 4 floats
 // (include/v3d.h, v3d_psv_variance_cl8): the split layout's addressing with the values themselves instead of bf16 pairs.
-template <bool SPLIT, bool CL8 = false>
+// WALK (depth walk, p.walk > 1): a wave keeps its 8 pixels for p.walk consecutive plane chunks.  WALK = false is the one-chunk
+// kernel as it was before the walk: no chunk loop, and none of what the walk does to stay inside the registers of
+// V3D_PSV_WAVES waves per SIMD (coordinates parked in LDS, values re-derived per chunk behind empty asm statements).
+template <bool SPLIT, bool CL8 = false, bool WALK = false>
 __global__ __launch_bounds__(SPLIT ? 64 : 256, V3D_PSV_WAVES) void psv_variance_window_kernel(PsvParams p) {
   static_assert(SPLIT || !CL8, "the channel-last fp32 output uses the single-wave geometry");
   constexpr int C = 32, WPB = SPLIT ? 1 : 4;
@@ -679,6 +685,7 @@ __global__ __launch_bounds__(SPLIT ? 64 : 256, V3D_PSV_WAVES) void psv_variance_
   __shared__ float s_ref_[WPB][24];
   __shared__ float s_P_[WPB][kMaxE][12];
   __shared__ int s_base_[WPB][kMaxE];
+  __shared__ __attribute__((aligned(16))) f32x4 s_xy_[WPB][WALK ? kRPix : 1];    // WALK: image coordinates (xf, yf) of the wave's 8 pixels
   // fp32 epilogue: [kOutPl][C][WPB * kRPix + 1] floats = 16.5 KB, parked on the four (by then dead) windows
   static_assert(SPLIT || kOutPl * C * (WPB * kRPix + 1) <= WPB * kWinRows * kWinCols * C, "epilogue staging fits the windows");
 
@@ -690,10 +697,14 @@ __global__ __launch_bounds__(SPLIT ? 64 : 256, V3D_PSV_WAVES) void psv_variance_
   float* const s_ref = s_ref_[wv];
   float (*const s_P)[12] = s_P_[wv];
   int* const s_base = s_base_[wv];
-  const int n_dchunk = (p.D + kRDB - 1) / kRDB;
+  f32x4* const s_xy = s_xy_[wv];
   const unsigned b = (unsigned)v3d::xcd_contiguous_block();
-  const unsigned b1 = v3d::udiv_magic(b, (unsigned)n_dchunk, p.m_dchunk), b2 = v3d::udiv_magic(b1, (unsigned)p.n_ptile, p.m_ptile);
-  const int dchunk = (int)(b - b1 * (unsigned)n_dchunk);     // plane chunks fastest (see the reuse kernel)
+  const unsigned b1 = v3d::udiv_magic(b, (unsigned)p.n_dseg, p.m_dseg), b2 = v3d::udiv_magic(b1, (unsigned)p.n_ptile, p.m_ptile);
+  const int dseg = (int)(b - b1 * (unsigned)p.n_dseg);       // depth segments fastest (see the reuse kernel)
+  // Depth walk: the wave keeps its 8 pixels for the chunks [c_begin, c_end) of its segment.  Between them only z differs: the
+  // reference camera, the edges' camera blocks, the index arithmetic, the pixel coordinates and every launch constant below
+  // are set up once per wave instead of once per chunk.
+  const int c_begin = WALK ? dseg * p.walk : dseg, c_end = WALK ? min(c_begin + p.walk, p.n_dchunk) : c_begin + 1;
   const int ptile = (int)(b1 - b2 * (unsigned)p.n_ptile) * WPB + wv;
   const int r = (int)b2;
   const int P = p.h * p.w;
@@ -701,13 +712,11 @@ __global__ __launch_bounds__(SPLIT ? 64 : 256, V3D_PSV_WAVES) void psv_variance_
   const int ne = e_end - e_begin;
   const int ref = p.ref_img[r];
   if (lane < 21) s_ref[lane] = p.camp[ref * kCamStride + lane];
-  psv_wave_sync<WPB>();
 
   // projection role: lane = (plane, pixel)
   const int pl1 = lane >> 3, px1 = lane & 7;
   const int gp1 = ptile * kRPix + px1;
-  const int d1 = dchunk * kRDB + pl1;
-  float X, Y, Z;
+  float xf1, yf1;                          // (WALK = false: the coordinates stay in registers)
   {
     // row / column of the lane's pixel: the wave's first pixel is divided once (wave-uniform), the lane adds its offset
     // (rows of at least kRPix pixels wrap at most once)
@@ -722,11 +731,15 @@ __global__ __launch_bounds__(SPLIT ? 64 : 256, V3D_PSV_WAVES) void psv_variance_
     }
     const float xf = (p.w > 1 && gx == p.w - 1) ? (float)(p.W - 1) : (float)((double)gx * p.x_step);
     const float yf = (p.h > 1 && gy == p.h - 1) ? (float)(p.H - 1) : (float)((double)gy * p.y_step);
-    const float z = (d1 == p.D - 1 && p.D > 1) ? (float)p.z_end : (float)(p.z_start + (double)d1 * p.z_step);
-    v3d::world_point(s_ref, xf, yf, z, X, Y, Z);
+    // parked in LDS for the walk (the lanes of plane 0 write; every chunk reads them back: one ds_read_b64 instead of two
+    // registers held across the whole kernel, which sits at the register limit of V3D_PSV_WAVES waves per SIMD)
+    if constexpr (WALK) { if (pl1 == 0) s_xy[px1] = (f32x4){xf, yf, 0.f, 0.f}; }
+    xf1 = xf; yf1 = yf;
   }
-  const bool live1 = gp1 < P && d1 < p.D;                   // lane 0 is always live
-  const bool all_live = __all(live1);
+  psv_wave_sync<WPB>();
+  // per chunk (set at the top of the chunk loop): the lane's world point, and whether its (pixel, plane) exists
+  float X, Y, Z;
+  bool live1, all_live;
   const float Wm1 = (float)(p.W - 1), Hm1 = (float)(p.H - 1);
   const float rWm1 = p.rWm1, rHm1 = p.rHm1;
   const float Wfm1 = (float)(p.Wf - 1), Hfm1 = (float)(p.Hf - 1);
@@ -744,8 +757,6 @@ __global__ __launch_bounds__(SPLIT ? 64 : 256, V3D_PSV_WAVES) void psv_variance_
   const unsigned win_lds = __builtin_amdgcn_readfirstlane(
       (unsigned)(size_t)(__attribute__((address_space(3))) void*)s_win);
   f32x4 acc_s[kRDB], acc_q[kRDB];
-#pragma unroll
-  for (int k = 0; k < kRDB; ++k) acc_s[k] = acc_q[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
 #if V3D_PSVW_ABLATE == 1
 #define V3D_PSV_BLEND(pl_, w_) asm volatile("" : : "v"(t00), "v"(t01), "v"(t10), "v"(t11), "v"(w_) : "memory")
@@ -775,8 +786,12 @@ __global__ __launch_bounds__(SPLIT ? 64 : 256, V3D_PSV_WAVES) void psv_variance_
   // camera blocks (P = K [R|t], first cell of the bordered map) of edges e0 .. e0 + 7
   auto load_cams = [&](int e0) __attribute__((always_inline)) {
     const int nload = min(kMaxE, ne - e0) * 12;
+    // (the lane index goes through an empty statement: the compiler otherwise works out the lane's addresses before the walk and
+    // holds them in vector registers across the whole kernel)
+    int lane0 = lane;
+    if constexpr (WALK) asm volatile("" : "+v"(lane0));
 #pragma unroll 1
-    for (int i = lane; i < nload; i += 64) {
+    for (int i = lane0; i < nload; i += 64) {
       const int src = p.edge_src[e_begin + e0 + i / 12];
       s_P[i / 12][i % 12] = p.camp[src * kCamStride + 24 + i % 12];
       if (i % 12 == 0) s_base[i / 12] = src * (p.Hf + 2) * Wp;      // cell (-1, -1) of the bordered map
@@ -813,188 +828,229 @@ __global__ __launch_bounds__(SPLIT ? 64 : 256, V3D_PSV_WAVES) void psv_variance_
   if (ne > 0) {
     load_cams(0);
     psv_wave_sync<WPB>();
-    project(0, xb, yb, wq);
   }
-  for (int e = 0; e < ne; ++e) {
-    psv_wave_sync<WPB>();                  // the previous pass is done with s_w / s_slot / s_win
-#ifdef V3D_PSV_NOPIPE                      // developer A/B: project at the top of the pass, wait for the copy right after issuing it
-    if (e > 0) {
-      if (e % kMaxE == 0) { load_cams(e); psv_wave_sync<WPB>(); }
-      project(e, xb, yb, wq);
-    }
-#endif
-    // Window = the box spanned by the four corner samples (first / last pixel on the first / last plane: a projective map is
-    // monotone in pixel and in depth, so they bound the 64 footprints in all but a few tiles), cut to 16 x 4 cells.  A
-    // sample whose footprint is not inside it is simply marked (bit 0 of its tap word) and takes its cells from featT.
-    int xmin, ymin, ncol, nrow;            // wave-uniform
+  const bool cnt_pow2 = (max(ne, 1) & (max(ne, 1) - 1)) == 0;
+  const int cg = lane & 7;
+
+  for (int dchunk = c_begin; dchunk < c_end; ++dchunk) {
+    const int d1 = dchunk * kRDB + pl1;
     {
-      // (both coordinates of a corner travel in one word: four lane reads instead of eight; bordered coordinates are >= 0)
-      const int cc = (yb << 16) | xb;
-      const int ca = __builtin_amdgcn_readlane(cc, 0), cb = __builtin_amdgcn_readlane(cc, 7);
-      const int cd = __builtin_amdgcn_readlane(cc, 56), ce = __builtin_amdgcn_readlane(cc, 63);
-      const int xa = ca & 0xffff, xc = cb & 0xffff, xd = cd & 0xffff, xe = ce & 0xffff;
-      const int ya = ca >> 16, yc = cb >> 16, yd = cd >> 16, ye = ce >> 16;
-      xmin = psv_smin(psv_smin(xa, xc), psv_smin(xd, xe));
-      ymin = psv_smin(psv_smin(ya, yc), psv_smin(yd, ye));
-      ncol = psv_smax(psv_smax(xa, xc), psv_smax(xd, xe)) - xmin + 2 > 8 ? kWinCols : 8;
-      nrow = psv_smin(psv_smax(psv_smax(ya, yc), psv_smax(yd, ye)) - ymin + 2, kWinRows);
-    }
-    const int base_cell = __builtin_amdgcn_readfirstlane(s_base[e % kMaxE]);
-    const unsigned dx = (unsigned)(xb - xmin), dy = (unsigned)(yb - ymin);
-    const bool inwin = dx <= (unsigned)(ncol - 2) && dy <= (unsigned)(nrow - 2);
-    // tap word: byte offset of the nw cell in the window, or -- sign bit set -- in featT (< 2 GB, checked by the host)
-    const unsigned so_win = ((dy << 4) | dx) * CB;
-    const unsigned so_ext = ((unsigned)(base_cell + __mul24(yb, Wp) + xb) * CB) | 0x80000000u;
-    const unsigned so = inwin ? so_win : so_ext;
-    s_w[lane] = wq;
-    s_slot[lane] = so;
-    // does ANY pixel change its footprint on plane k (bit group k of the ballot)?  plane 0 always loads
-    const unsigned prev = (unsigned)__builtin_amdgcn_ds_bpermute(((lane - 8) & 63) * 4, (int)so);
-    const unsigned long long chg = __ballot(lane < 8 || so != prev);
-    // copy the window: nrow rows of 8 or 16 cells from (xmin, ymin) (runs past the last needed column stay inside the bordered
-    // maps + tail); lane l moves bytes [16 l, 16 l + 16) of each 1 KB run
-    {
-      // wave-uniform row address (SGPR pair) + the lane's 16 bytes (one constant VGPR): no per-lane address arithmetic.  The
-      // copies are written in assembly (hipcc forms 64-bit per-lane addresses for the builtin): M0 = LDS byte address of the
-      // run, saved and restored around each copy; the wave waits for them itself (vmcnt below).
-      const char* rowp = fb + (size_t)((unsigned)(base_cell + ymin * Wp + xmin) * CB);
-      unsigned dst = win_lds;
-      asm volatile("s_nop 4" ::: "memory");            // SGPRs written by v_readlane may feed the first copy's address
-#pragma unroll 1
-      for (int rr = 0; rr < (V3D_PSVW_ABLATE == 3 ? 0 : nrow); ++rr) {
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(lane16), "s"(rowp), "s"(dst) : "memory");
-        if (ncol > 8)
-          asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\ts_mov_b32 m0, %0"
-                       : "=&s"(keep) : "v"(lane16), "s"(rowp), "s"(dst) : "memory");   // the instruction offset moves BOTH addresses
-        rowp += (size_t)Wp * CB;
-        dst += kWinCols * CB;
+      // (the empty statement keeps the plane range in scalar registers: hoisted out of the walk, its vector-register copies
+      // are live across the whole kernel and spill)
+      double z_start = p.z_start, z_end = p.z_end;
+      if constexpr (WALK) asm volatile("" : "+s"(z_start), "+s"(z_end));
+      const float z = (d1 == p.D - 1 && p.D > 1) ? (float)z_end : (float)(z_start + (double)d1 * p.z_step);
+      if constexpr (WALK) {
+        const f32x4 xy = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(s_xy) + cgb);      // s_xy[px1]
+        xf1 = xy[0]; yf1 = xy[1];
       }
+      v3d::world_point(s_ref, xf1, yf1, z, X, Y, Z);
     }
-#ifndef V3D_PSV_NOPIPE
-    if (e + 1 < ne) {
-      if ((e + 1) % kMaxE == 0) {
-        psv_wave_sync<WPB>();
-        load_cams(e + 1);
-        psv_wave_sync<WPB>();
-      }
-      project(e + 1, xb, yb, wq);
-    }
-#endif
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // the window has landed, the tap records are written
-    psv_wave_sync<WPB>();
-    // deliberately not initialised: the first plane of a pass always loads them
-    f32x4 t00, t01, t10, t11;
-    f32x4 wn = s_w[gpx];
-    unsigned sn = s_slot[gpx];
+    live1 = gp1 < P && d1 < p.D;                              // lane 0 is always live
+    all_live = __all(live1);
 #pragma unroll
-    for (int pl = 0; pl < kRDB; ++pl) {
-      const f32x4 w = wn;
-      const unsigned so_pl = sn;
-      if (pl + 1 < kRDB) {               // next plane's record: in flight during this plane's blend
-        wn = s_w[(pl + 1) * kRPix + gpx];
-        sn = s_slot[(pl + 1) * kRPix + gpx];
+    for (int k = 0; k < kRDB; ++k) acc_s[k] = acc_q[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (ne > 0) {
+      // more edges than s_P holds: the previous chunk's last pass left edges 8.. there
+      if (ne > kMaxE && dchunk != c_begin) {
+        psv_wave_sync<WPB>();
+        load_cams(0);
+        psv_wave_sync<WPB>();
       }
-      if (((chg >> (8 * pl)) & 0xffull) && (V3D_PSVW_ABLATE != 2 || (pl == 0 && e == 0))) {      // wave-uniform: all pixels reload together (a load costs the same masked or not)
-        // (a wave-uniform test "no sample of this plane is outside the window" -- one ballot per pass -- in front of the per-lane
-        // sign test saves a v_cmp and the exec-mask juggling in 95 % of the planes and measured 0.6 % SLOWER, round 4)
-        if (V3D_PSVW_ABLATE != 6 && (int)so_pl < 0) {
-          const unsigned b00 = so_pl & 0x7fffffffu;
-          t00 = *reinterpret_cast<const f32x4*>(fb + (size_t)(b00 + cgb));
-          t01 = *reinterpret_cast<const f32x4*>(fb + (size_t)(b00 + cgb) + CB);
-          t10 = *reinterpret_cast<const f32x4*>(fb + (size_t)(b00 + rowb));
-          t11 = *reinterpret_cast<const f32x4*>(fb + (size_t)(b00 + rowb) + CB);
-        } else {
-          const char* a = wb + (so_pl + cgb);
-          t00 = *reinterpret_cast<const f32x4*>(a);
-          t01 = *reinterpret_cast<const f32x4*>(a + CB);
-          t10 = *reinterpret_cast<const f32x4*>(a + kWinCols * CB);
-          t11 = *reinterpret_cast<const f32x4*>(a + kWinCols * CB + CB);
+      project(0, xb, yb, wq);
+    }
+    for (int e = 0; e < ne; ++e) {
+      psv_wave_sync<WPB>();                  // the previous pass is done with s_w / s_slot / s_win
+#ifdef V3D_PSV_NOPIPE                      // developer A/B: project at the top of the pass, wait for the copy right after issuing it
+      if (e > 0) {
+        if (e % kMaxE == 0) { load_cams(e); psv_wave_sync<WPB>(); }
+        project(e, xb, yb, wq);
+      }
+#endif
+      // Window = the box spanned by the four corner samples (first / last pixel on the first / last plane: a projective map is
+      // monotone in pixel and in depth, so they bound the 64 footprints in all but a few tiles), cut to 16 x 4 cells.  A
+      // sample whose footprint is not inside it is simply marked (bit 0 of its tap word) and takes its cells from featT.
+      int xmin, ymin, ncol, nrow;            // wave-uniform
+      {
+        // (both coordinates of a corner travel in one word: four lane reads instead of eight; bordered coordinates are >= 0)
+        const int cc = (yb << 16) | xb;
+        const int ca = __builtin_amdgcn_readlane(cc, 0), cb = __builtin_amdgcn_readlane(cc, 7);
+        const int cd = __builtin_amdgcn_readlane(cc, 56), ce = __builtin_amdgcn_readlane(cc, 63);
+        const int xa = ca & 0xffff, xc = cb & 0xffff, xd = cd & 0xffff, xe = ce & 0xffff;
+        const int ya = ca >> 16, yc = cb >> 16, yd = cd >> 16, ye = ce >> 16;
+        xmin = psv_smin(psv_smin(xa, xc), psv_smin(xd, xe));
+        ymin = psv_smin(psv_smin(ya, yc), psv_smin(yd, ye));
+        ncol = psv_smax(psv_smax(xa, xc), psv_smax(xd, xe)) - xmin + 2 > 8 ? kWinCols : 8;
+        nrow = psv_smin(psv_smax(psv_smax(ya, yc), psv_smax(yd, ye)) - ymin + 2, kWinRows);
+      }
+      const int base_cell = __builtin_amdgcn_readfirstlane(s_base[e % kMaxE]);
+      const unsigned dx = (unsigned)(xb - xmin), dy = (unsigned)(yb - ymin);
+      const bool inwin = dx <= (unsigned)(ncol - 2) && dy <= (unsigned)(nrow - 2);
+      // tap word: byte offset of the nw cell in the window, or -- sign bit set -- in featT (< 2 GB, checked by the host)
+      const unsigned so_win = ((dy << 4) | dx) * CB;
+      const unsigned so_ext = ((unsigned)(base_cell + __mul24(yb, Wp) + xb) * CB) | 0x80000000u;
+      const unsigned so = inwin ? so_win : so_ext;
+      s_w[lane] = wq;
+      s_slot[lane] = so;
+      // does ANY pixel change its footprint on plane k (bit group k of the ballot)?  plane 0 always loads
+      const unsigned prev = (unsigned)__builtin_amdgcn_ds_bpermute(((lane - 8) & 63) * 4, (int)so);
+      const unsigned long long chg = __ballot(lane < 8 || so != prev);
+      // copy the window: nrow rows of 8 or 16 cells from (xmin, ymin) (runs past the last needed column stay inside the bordered
+      // maps + tail); lane l moves bytes [16 l, 16 l + 16) of each 1 KB run
+      {
+        // wave-uniform row address (SGPR pair) + the lane's 16 bytes (one constant VGPR): no per-lane address arithmetic.  The
+        // copies are written in assembly (hipcc forms 64-bit per-lane addresses for the builtin): M0 = LDS byte address of the
+        // run, saved and restored around each copy; the wave waits for them itself (vmcnt below).
+        const char* rowp = fb + (size_t)((unsigned)(base_cell + ymin * Wp + xmin) * CB);
+        unsigned dst = win_lds;
+        asm volatile("s_nop 4" ::: "memory");            // SGPRs written by v_readlane may feed the first copy's address
+#pragma unroll 1
+        for (int rr = 0; rr < (V3D_PSVW_ABLATE == 3 ? 0 : nrow); ++rr) {
+          unsigned keep;
+          asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                       : "=&s"(keep) : "v"(lane16), "s"(rowp), "s"(dst) : "memory");
+          if (ncol > 8)
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\ts_mov_b32 m0, %0"
+                         : "=&s"(keep) : "v"(lane16), "s"(rowp), "s"(dst) : "memory");   // the instruction offset moves BOTH addresses
+          rowp += (size_t)Wp * CB;
+          dst += kWinCols * CB;
         }
       }
-      V3D_PSV_BLEND(pl, w);
+#ifndef V3D_PSV_NOPIPE
+      if (e + 1 < ne) {
+        if ((e + 1) % kMaxE == 0) {
+          psv_wave_sync<WPB>();
+          load_cams(e + 1);
+          psv_wave_sync<WPB>();
+        }
+        project(e + 1, xb, yb, wq);
+      }
+#endif
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // the window has landed, the tap records are written
+      psv_wave_sync<WPB>();
+      // deliberately not initialised: the first plane of a pass always loads them
+      f32x4 t00, t01, t10, t11;
+      f32x4 wn = s_w[gpx];
+      unsigned sn = s_slot[gpx];
+#pragma unroll
+      for (int pl = 0; pl < kRDB; ++pl) {
+        const f32x4 w = wn;
+        const unsigned so_pl = sn;
+        if (pl + 1 < kRDB) {               // next plane's record: in flight during this plane's blend
+          wn = s_w[(pl + 1) * kRPix + gpx];
+          sn = s_slot[(pl + 1) * kRPix + gpx];
+        }
+        if (((chg >> (8 * pl)) & 0xffull) && (V3D_PSVW_ABLATE != 2 || (pl == 0 && e == 0))) {      // wave-uniform: all pixels reload together (a load costs the same masked or not)
+          // (a wave-uniform test "no sample of this plane is outside the window" -- one ballot per pass -- in front of the per-lane
+          // sign test saves a v_cmp and the exec-mask juggling in 95 % of the planes and measured 0.6 % SLOWER, round 4)
+          if (V3D_PSVW_ABLATE != 6 && (int)so_pl < 0) {
+            const unsigned b00 = so_pl & 0x7fffffffu;
+            t00 = *reinterpret_cast<const f32x4*>(fb + (size_t)(b00 + cgb));
+            t01 = *reinterpret_cast<const f32x4*>(fb + (size_t)(b00 + cgb) + CB);
+            t10 = *reinterpret_cast<const f32x4*>(fb + (size_t)(b00 + rowb));
+            t11 = *reinterpret_cast<const f32x4*>(fb + (size_t)(b00 + rowb) + CB);
+          } else {
+            const char* a = wb + (so_pl + cgb);
+            t00 = *reinterpret_cast<const f32x4*>(a);
+            t01 = *reinterpret_cast<const f32x4*>(a + CB);
+            t10 = *reinterpret_cast<const f32x4*>(a + kWinCols * CB);
+            t11 = *reinterpret_cast<const f32x4*>(a + kWinCols * CB + CB);
+          }
+        }
+        V3D_PSV_BLEND(pl, w);
+      }
     }
-  }
-#undef V3D_PSV_BLEND
 
-  // ---- variance -> stores (as in the reuse kernel) -------------------------------------------------------------
-  psv_wave_sync<WPB>();
-  const float cnt = (float)max(ne, 1);        // torch_scatter mean: sum / clamp(count, 1)
-  const bool cnt_pow2 = (max(ne, 1) & (max(ne, 1) - 1)) == 0;
-  const float cnt_inv = 1.f / cnt;
-  const int cg = lane & 7;
-  if constexpr (SPLIT) {
-    const int chunk = cg >> 1, half = cg & 1;
-    u32x4* const out = reinterpret_cast<u32x4*>(p.var);
-    const int gp = ptile * kRPix + gpx;
-    // the lane's slot on the chunk's first plane; plane pl is pl * P slots further (a wave-uniform stride: with the whole
-    // index spelled out per plane the compiler rebuilt the 64-bit product -- two v_mul_lo_u32 and a v_mad_u64_u32 -- eight times)
-    u32x4* const obase = out + (((size_t)r * 8 + chunk * 2 + half) * p.D + (size_t)dchunk * kRDB) * P + gp;
-    // x / cnt is an IEEE division; for a power-of-two count x * (1 / cnt) is the same number exactly.  ONE wave-uniform
-    // branch around the whole epilogue (the reuse kernel tests it per value: 64 branches)
+    // ---- variance -> stores (as in the reuse kernel) -------------------------------------------------------------
+    psv_wave_sync<WPB>();
+    // (the thread index of the store addresses goes through an empty statement, as in load_cams: worked out before the walk, the
+    // lanes' 64-bit addresses would be held in vector registers across the whole kernel)
+    int tid_o = (int)threadIdx.x;
+    if constexpr (WALK) asm volatile("" : "+v"(tid_o));
+    int ne_o = ne;                                // (likewise the mean's divisor and its reciprocal: a dozen instructions per chunk)
+    if constexpr (WALK) asm volatile("" : "+s"(ne_o));
+    const float cnt = (float)max(ne_o, 1);        // torch_scatter mean: sum / clamp(count, 1)
+    const float cnt_inv = 1.f / cnt;
+    if constexpr (SPLIT) {
+      const int chunk = cg >> 1, half = cg & 1;
+      u32x4* const out = reinterpret_cast<u32x4*>(p.var);
+      const int gp = ptile * kRPix + (tid_o >> 3);
+      // the lane's slot on the chunk's first plane; plane pl is pl * P slots further (a wave-uniform stride: with the whole
+      // index spelled out per plane the compiler rebuilt the 64-bit product -- two v_mul_lo_u32 and a v_mad_u64_u32 -- eight times).
+      // WALK: wave-uniform 64-bit part + the lane's 32-bit slot inside its view's volume (8 D P slots < 2^32, checked by the
+      // host): nothing of it is held in vector registers across the walk.
+      u32x4* const obase = WALK ? out + ((size_t)r * 8 * p.D + (size_t)dchunk * kRDB) * P +
+                                      ((unsigned)(chunk * 2 + half) * (unsigned)(p.D * P) + (unsigned)gp)
+                                : out + (((size_t)r * 8 + chunk * 2 + half) * p.D + (size_t)dchunk * kRDB) * P + gp;
+      // x / cnt is an IEEE division; for a power-of-two count x * (1 / cnt) is the same number exactly.  ONE wave-uniform
+      // branch around the whole epilogue (the reuse kernel tests it per value: 64 branches)
 #define V3D_PSV_EMIT(MEAN)                                                                                              \
-  _Pragma("unroll") for (int pl = 0; pl < kRDB; ++pl) {                                                                 \
-    float v[4];                                                                                                         \
-    _Pragma("unroll") for (int k = 0; k < 4; ++k) {                                                                     \
-      const float avg = MEAN(acc_s[pl][k]);                                                                             \
-      const float avg_sq = MEAN(acc_q[pl][k]);                                                                          \
-      v[k] = v3d::sub_rn(avg_sq, v3d::mul_rn(avg, avg));                    /* mvsnet.py:216 */                         \
-    }                                                                                                                   \
-    const int d = dchunk * kRDB + pl;                                                                                   \
-    if constexpr (CL8) {                                                                                                \
-      /* channels 4 cg .. 4 cg + 3 = half `half` of the voxel's channel group `chunk`: the lane's own 16 bytes */         \
-      const u32x4 slot = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};  \
-      if (gp < P && d < p.D)                                                                                            \
+    _Pragma("unroll") for (int pl = 0; pl < kRDB; ++pl) {                                                               \
+      float v[4];                                                                                                       \
+      _Pragma("unroll") for (int k = 0; k < 4; ++k) {                                                                   \
+        const float avg = MEAN(acc_s[pl][k]);                                                                           \
+        const float avg_sq = MEAN(acc_q[pl][k]);                                                                        \
+        v[k] = v3d::sub_rn(avg_sq, v3d::mul_rn(avg, avg));                    /* mvsnet.py:216 */                       \
+      }                                                                                                                 \
+      const int d = dchunk * kRDB + pl;                                                                                 \
+      if constexpr (CL8) {                                                                                              \
+        /* channels 4 cg .. 4 cg + 3 = half `half` of the voxel's channel group `chunk`: the lane's own 16 bytes */       \
+        const u32x4 slot = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};\
+        if (gp < P && d < p.D)                                                                                          \
+          __builtin_nontemporal_store(slot, obase + (size_t)pl * (unsigned)P);                                           \
+      } else {                                                                                                          \
+      const unsigned h01 = pack_bf16x2(v[0], v[1]), h23 = pack_bf16x2(v[2], v[3]);                                      \
+      const unsigned l01 = pack_bf16x2(v[0] - __uint_as_float(h01 << 16), v[1] - __uint_as_float(h01 & 0xffff0000u));   \
+      const unsigned l23 = pack_bf16x2(v[2] - __uint_as_float(h23 << 16), v[3] - __uint_as_float(h23 & 0xffff0000u));   \
+      const unsigned s0 = half ? h01 : l01, s1 = half ? h23 : l23;             /* what the partner lane stores */        \
+      const unsigned r0 = (unsigned)__builtin_amdgcn_mov_dpp((int)s0, 0xB1, 0xf, 0xf, true);   /* quad_perm [1,0,3,2] */ \
+      const unsigned r1 = (unsigned)__builtin_amdgcn_mov_dpp((int)s1, 0xB1, 0xf, 0xf, true);                            \
+      const u32x4 slot = half ? (u32x4){r0, r1, l01, l23} : (u32x4){h01, h23, r0, r1};                                  \
+      if (gp < P && d < p.D && (V3D_PSVW_ABLATE != 5 || slot[0] == 0x12345u))                                           \
         __builtin_nontemporal_store(slot, obase + (size_t)pl * (unsigned)P);                                             \
-    } else {                                                                                                            \
-    const unsigned h01 = pack_bf16x2(v[0], v[1]), h23 = pack_bf16x2(v[2], v[3]);                                        \
-    const unsigned l01 = pack_bf16x2(v[0] - __uint_as_float(h01 << 16), v[1] - __uint_as_float(h01 & 0xffff0000u));     \
-    const unsigned l23 = pack_bf16x2(v[2] - __uint_as_float(h23 << 16), v[3] - __uint_as_float(h23 & 0xffff0000u));     \
-    const unsigned s0 = half ? h01 : l01, s1 = half ? h23 : l23;             /* what the partner lane stores */          \
-    const unsigned r0 = (unsigned)__builtin_amdgcn_mov_dpp((int)s0, 0xB1, 0xf, 0xf, true);   /* quad_perm [1,0,3,2] */   \
-    const unsigned r1 = (unsigned)__builtin_amdgcn_mov_dpp((int)s1, 0xB1, 0xf, 0xf, true);                              \
-    const u32x4 slot = half ? (u32x4){r0, r1, l01, l23} : (u32x4){h01, h23, r0, r1};                                    \
-    if (gp < P && d < p.D && (V3D_PSVW_ABLATE != 5 || slot[0] == 0x12345u))                                             \
-      __builtin_nontemporal_store(slot, obase + (size_t)pl * (unsigned)P);                                               \
-    }                                                                                                                   \
-  }
+      }                                                                                                                 \
+    }
 #define V3D_MEAN_MUL(x) ((x) * cnt_inv)
-    // any other count: the correctly rounded quotient from the correctly rounded reciprocal (v3d::div_uniform, Markstein;
-    // 4 instructions instead of the 11 of the IEEE sequence, twice per output value); v_div_fixup restores the special cases
+      // any other count: the correctly rounded quotient from the correctly rounded reciprocal (v3d::div_uniform, Markstein;
+      // 4 instructions instead of the 11 of the IEEE sequence, twice per output value); v_div_fixup restores the special cases
 #define V3D_MEAN_DIV(x) __builtin_amdgcn_div_fixupf(v3d::div_uniform((x), cnt, cnt_inv), cnt, (x))
-    if (cnt_pow2) { V3D_PSV_EMIT(V3D_MEAN_MUL) } else { V3D_PSV_EMIT(V3D_MEAN_DIV) }
+      if (cnt_pow2) { V3D_PSV_EMIT(V3D_MEAN_MUL) } else { V3D_PSV_EMIT(V3D_MEAN_DIV) }
 #undef V3D_PSV_EMIT
 #undef V3D_MEAN_MUL
 #undef V3D_MEAN_DIV
-  } else {
-    constexpr int NPX = WPB * kRPix;
-    float (*const s_out)[C][NPX + 1] = reinterpret_cast<float (*)[C][NPX + 1]>(&s_win_[0][0]);
-    auto mean = [&](float x) __attribute__((always_inline)) {
-      return cnt_pow2 ? x * cnt_inv : __builtin_amdgcn_div_fixupf(v3d::div_uniform(x, cnt, cnt_inv), cnt, x);
-    };
-    const int gp0 = (ptile - wv) * kRPix;             // first pixel of the workgroup
+    } else {
+      constexpr int NPX = WPB * kRPix;
+      float (*const s_out)[C][NPX + 1] = reinterpret_cast<float (*)[C][NPX + 1]>(&s_win_[0][0]);
+      auto mean = [&](float x) __attribute__((always_inline)) {
+        return cnt_pow2 ? x * cnt_inv : __builtin_amdgcn_div_fixupf(v3d::div_uniform(x, cnt, cnt_inv), cnt, x);
+      };
+      const int gp0 = (ptile - wv) * kRPix;             // first pixel of the workgroup
 #pragma unroll
-    for (int round = 0; round < kRDB / kOutPl; ++round) {
-      __syncthreads();                                 // every wave is done with its window / the previous round is stored
+      for (int round = 0; round < kRDB / kOutPl; ++round) {
+        __syncthreads();                                 // every wave is done with its window / the previous round is stored
 #pragma unroll
-      for (int q = 0; q < kOutPl; ++q) {
-        const int pl = round * kOutPl + q;
+        for (int q = 0; q < kOutPl; ++q) {
+          const int pl = round * kOutPl + q;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float avg = mean(acc_s[pl][k]);
-          const float avg_sq = mean(acc_q[pl][k]);
-          s_out[q][cg * 4 + k][wv * kRPix + gpx] = v3d::sub_rn(avg_sq, v3d::mul_rn(avg, avg));   // mvsnet.py:216
+          for (int k = 0; k < 4; ++k) {
+            const float avg = mean(acc_s[pl][k]);
+            const float avg_sq = mean(acc_q[pl][k]);
+            s_out[q][cg * 4 + k][wv * kRPix + gpx] = v3d::sub_rn(avg_sq, v3d::mul_rn(avg, avg));   // mvsnet.py:216
+          }
+        }
+        __syncthreads();
+        for (int i = tid_o; i < kOutPl * C * NPX; i += 64 * WPB) {
+          const int q = i / (C * NPX), c = (i / NPX) % C, px = i % NPX;
+          const int gp = gp0 + px, d = dchunk * kRDB + round * kOutPl + q;
+          if (gp < P && d < p.D) __builtin_nontemporal_store(s_out[q][c][px], &p.var[(((size_t)r * C + c) * p.D + d) * P + gp]);
         }
       }
-      __syncthreads();
-      for (int i = threadIdx.x; i < kOutPl * C * NPX; i += 64 * WPB) {
-        const int q = i / (C * NPX), c = (i / NPX) % C, px = i % NPX;
-        const int gp = gp0 + px, d = dchunk * kRDB + round * kOutPl + q;
-        if (gp < P && d < p.D) __builtin_nontemporal_store(s_out[q][c][px], &p.var[(((size_t)r * C + c) * p.D + d) * P + gp]);
-      }
+      // the staged rows live on the windows: all four waves (they walk the same segment) have read them before the next chunk's
+      // window copies land there
+      if (WALK && dchunk + 1 < c_end) __syncthreads();
     }
-  }
+  }      // chunk loop
+#undef V3D_PSV_BLEND
 }
 
 // Diagnostic twin of the warp kernels' projection (v3d_psv_sample_positions_f32): one thread per (edge, plane, pixel)
@@ -1048,6 +1104,25 @@ static size_t psv_feat_bytes(int n_img, int C, int Hf, int Wf) {
 extern "C" size_t v3d_psv_workspace_bytes(int n_img, int C, int Hf, int Wf) {
   // channel-last copy of the feature maps + the per-image camera blocks
   return v3d::align_up(psv_feat_bytes(n_img, C, Hf, Wf), 256) + v3d::align_up((size_t)n_img * kCamStride * sizeof(float), 256);
+}
+
+// Window kernel: plane chunks a wave walks (PsvParams::walk).  A longer walk spreads the per-wave set-up over more chunks but
+// leaves fewer, longer waves, i.e. a longer tail behind the last full round of resident waves.  The rule is a function of the
+// shape alone -- the same for every call of a shape: the longest walk that keeps the launch at kMinRounds rounds of the
+// kResident waves an MI355X holds (256 CUs x 4 SIMDs x V3D_PSV_WAVES), evened out over the segments (5 chunks at a walk of
+// 4 are 3 + 2, not 4 + 1).  `forced` > 0 (developer option "psv_walk") overrides it.
+static int psv_walk_chunks(int forced, int n_dchunk, int n_ref, int n_ptile) {
+  constexpr long long kResident = 256 * 4 * V3D_PSV_WAVES, kMinRounds = 16;
+  long long walk = forced > 0 ? forced : (long long)n_ref * n_dchunk * n_ptile / (kMinRounds * kResident);
+  walk = walk < 1 ? 1 : walk > n_dchunk ? n_dchunk : walk;
+  if (forced > 0) return (int)walk;
+  const long long n_dseg = (n_dchunk + walk - 1) / walk;
+  return (int)((n_dchunk + n_dseg - 1) / n_dseg);
+}
+
+extern "C" int v3d_psv_walk_chunks(int n_ref, int D, int h, int w) {
+  V3D_REQUIRE(n_ref > 0 && D > 0 && h > 0 && w > 0, V3D_ERR_BAD_SHAPE, "v3d_psv_walk_chunks: bad shape");
+  return psv_walk_chunks(v3d::option(v3d::kOptPsvWalk), (D + kRDB - 1) / kRDB, n_ref, (h * w + kRPix - 1) / kRPix);
 }
 
 static int psv_variance_impl(int mode, const float* feat, const float* K, const float* R,
@@ -1119,26 +1194,37 @@ static int psv_variance_impl(int mode, const float* feat, const float* K, const 
       const bool no_window = reuse_env || psv_feat_bytes(n_img, C, Hf, Wf) >= ((size_t)1 << 31);
       V3D_REQUIRE(!cl8 || !no_window, V3D_ERR_UNSUPPORTED,
                   "v3d_psv_variance_cl8: only the window kernel writes this layout (feature maps < 2 GB, no developer switch)");
+      unsigned wblocks = 0;      // grid of the window kernel: (view, pixel tile group, depth segment)
       {      // launch constants of the window kernel (PsvParams)
         const unsigned ndc = (unsigned)((D + kRDB - 1) / kRDB);
         const unsigned npt = (unsigned)(split || cl8 ? p.n_ptile : (p.n_ptile + 3) / 4);
-        const unsigned long long nblk = (unsigned long long)n_ref * ndc * npt;
+        p.n_dchunk = (int)ndc;
+        p.walk = psv_walk_chunks(v3d::option(v3d::kOptPsvWalk), (int)ndc, n_ref, p.n_ptile);
+        // the walking kernel addresses a lane's split / cl8 output slot inside its view's volume with 32 bits
+        if ((split || cl8) && 8ull * D * h * w >= (1ull << 32)) p.walk = 1;
+        p.n_dseg = ((int)ndc + p.walk - 1) / p.walk;
+        const unsigned long long nblk = (unsigned long long)n_ref * p.n_dseg * npt;
+        wblocks = (unsigned)nblk;
         p.rWm1 = (float)(1.0 / (double)(W - 1));
         p.rHm1 = (float)(1.0 / (double)(H - 1));
-        p.m_dchunk = v3d::magic_u32(nblk, ndc);
-        p.m_ptile = v3d::magic_u32(nblk / ndc + 1, npt);
+        p.m_dseg = v3d::magic_u32(nblk, (unsigned)p.n_dseg);
+        p.m_ptile = v3d::magic_u32(nblk / p.n_dseg + 1, npt);
         p.m_w = v3d::magic_u32((unsigned long long)h * w + 4 * kRPix, (unsigned)w);
       }
+      const bool walk = p.walk > 1;      // one chunk per wave: the kernel without the walk's bookkeeping
       if (cl8) {
-        psv_variance_window_kernel<true, true><<<(unsigned)rblocks, 64, 0, s>>>(p);
+        if (walk) psv_variance_window_kernel<true, true, true><<<wblocks, 64, 0, s>>>(p);
+        else psv_variance_window_kernel<true, true, false><<<wblocks, 64, 0, s>>>(p);
       } else if (split) {
         if (no_window) psv_variance_reuse_kernel<true><<<(unsigned)rblocks, 64, 0, s>>>(p);
-        else psv_variance_window_kernel<true><<<(unsigned)rblocks, 64, 0, s>>>(p);
+        else if (walk) psv_variance_window_kernel<true, false, true><<<wblocks, 64, 0, s>>>(p);
+        else psv_variance_window_kernel<true, false, false><<<wblocks, 64, 0, s>>>(p);
       } else {      // four 8-pixel tiles per workgroup
         p.n_ptile = (p.n_ptile + 3) / 4;
         const long long fblocks = (long long)n_ref * ((D + kRDB - 1) / kRDB) * p.n_ptile;
         if (no_window) psv_variance_reuse_kernel<false><<<(unsigned)fblocks, 256, 0, s>>>(p);
-        else psv_variance_window_kernel<false><<<(unsigned)fblocks, 256, 0, s>>>(p);
+        else if (walk) psv_variance_window_kernel<false, false, true><<<wblocks, 256, 0, s>>>(p);
+        else psv_variance_window_kernel<false, false, false><<<wblocks, 256, 0, s>>>(p);
       }
     } else if (cl8) {
       return v3d::fail(V3D_ERR_UNSUPPORTED, "v3d_psv_variance_cl8: C=%d unsupported (32) / option psv_kernel = 2", C);

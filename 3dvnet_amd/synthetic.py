@@ -277,3 +277,17 @@ def make_costvolume_inputs(cfg_name, n_ref, feat_dim=32, seed=None):
     cfg.update(feat=feat, rotmats=rotmats, tvecs=tvecs, K=K, edges=edges, n_img=n_img,
                n_ref=n_ref)
     return cfg
+
+
+def make_exotic_cameras(img_size=(64, 80), seed=9):
+    """Six cameras whose pairs defeat the window warp kernel's 16 x 4-cell window (scripts/psv_hash.py,
+    scripts/psv_walk_dump.py): source 1 zoomed 3x (pixels 4 cells apart), source 2 rolled by 90 degrees (rows become
+    columns), source 3 far off to the side (long epipolar slides)."""
+    R, tv, K = make_cameras(6, img_size, seed=seed)
+    K = K.clone(); K[1, 0, 0] *= 3.0; K[1, 1, 1] *= 3.0
+    c, s_ = math.cos(math.pi / 2), math.sin(math.pi / 2)
+    roll = torch.tensor([[c, -s_, 0.0], [s_, c, 0.0], [0.0, 0.0, 1.0]])
+    R = R.clone(); tv = tv.clone()
+    R[2] = roll @ R[2]; tv[2] = roll @ tv[2]
+    tv[3] = tv[3] + torch.tensor([0.8, 0.0, 0.0])
+    return R, tv, K

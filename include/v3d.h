@@ -54,7 +54,9 @@ extern "C" {
  *   "stop_after"      layer after which v3d_costreg_depth_* returns (-DV3D_PHASE_TIMING builds)
  *   "gemm_rounds"     1 | 0      gather-GEMM in rounds for small M | the one-step kernel (bit-identical)
  *   "gemm_pipe"       1 | 0      sparse convolutions on the loader / matrix pipeline kernel | the rounds kernel (bit-identical)
- * Unknown names, and gemm_rounds / gemm_pipe values other than 0 and 1 -> V3D_ERR_BAD_ARG. */
+ *   "psv_walk"        0 | N      plane chunks (of 8 planes) a wave of the window warp kernel walks: chosen from the shape | N (bit-identical)
+ * Unknown names, gemm_rounds / gemm_pipe values other than 0 and 1, and a negative psv_walk -> V3D_ERR_BAD_ARG.
+ * ("psv_walk" is additive within ABI version 9: a new option name, no changed signature; v3d_version() is not bumped.) */
 int v3d_set_option(const char* name, int value);
 int v3d_get_option(const char* name, int* value);
 
@@ -110,6 +112,10 @@ int v3d_edges_csr_status(const void* workspace, size_t workspace_bytes, void* st
  *   workspace >= v3d_psv_workspace_bytes(n_img, C, Hf, Wf) bytes, 256-byte aligned
  * ------------------------------------------------------------------------------------------ */
 size_t v3d_psv_workspace_bytes(int n_img, int C, int Hf, int Wf);
+/* Diagnostic (no reference counterpart): the number of consecutive 8-plane chunks a wave of the window warp kernel walks for a
+ * launch of n_ref views, D planes and an h x w plane grid -- a function of the shape alone, or the developer option "psv_walk"
+ * when that is set; at most the number of chunks.  Additive within ABI version 9. */
+int v3d_psv_walk_chunks(int n_ref, int D, int h, int w);
 int v3d_psv_variance_f32(const float* feat, const float* K, const float* R, const float* t,
                          const int32_t* ref_img, const int32_t* edge_ofs, const int32_t* edge_src,
                          int n_img, int n_ref, int n_edges, int C, int Hf, int Wf, int H, int W,

@@ -34,14 +34,7 @@ var = mvs.plane_sweep_variance(feat.to(dev), R, tv, K, edges.to(dev), 0.5, 0.2, 
 print('7-edge', hashlib.sha256(var.cpu().numpy().tobytes()).hexdigest()[:16], float(var.double().sum()))
 
 # windows that cannot hold the footprints: every sample (or most) takes the out-of-window path of the window kernel
-import math
-R, tv, K = syn.make_cameras(6, (64, 80), seed=9)
-K = K.clone(); K[1, 0, 0] *= 3.0; K[1, 1, 1] *= 3.0                       # source 1: zoomed 3x (pixels 4 cells apart)
-c, s_ = math.cos(math.pi / 2), math.sin(math.pi / 2)
-roll = torch.tensor([[c, -s_, 0.0], [s_, c, 0.0], [0.0, 0.0, 1.0]])
-R = R.clone(); tv = tv.clone()
-R[2] = roll @ R[2]; tv[2] = roll @ tv[2]                                  # source 2: rolled by 90 degrees (rows become columns)
-tv[3] = tv[3] + torch.tensor([0.8, 0.0, 0.0])                             # source 3: far off to the side (long epipolar slides)
+R, tv, K = syn.make_exotic_cameras((64, 80), seed=9)      # source 1 zoomed 3x, source 2 rolled by 90 degrees, source 3 far off to the side
 feat = syn.make_features(6, 32, 16, 20, seed=9)
 edges = torch.tensor([[0] * 5 + [4] * 3, [0, 1, 2, 3, 5, 4, 1, 2]])
 for split in (False, True):

@@ -148,6 +148,8 @@ SIGNATURES = {
     'v3d_mesh_count_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'v3d_mesh_extract_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_float_p, c_int, c_void_p, c_void_p, c_int,
                                      c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    'v3d_mesh_render_depth_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_double, c_double,
+                                          c_double, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -80,6 +80,8 @@ def build(force=False, verbose=False, strict=False):
             isa_check.check_no_scratch(os.path.join(objdir, 'cloudmetrics.o'), 'nn_query_kernel', strict=strict)
             # mesh extraction: the status bytes of a cell, its table row and the vertex state stay in registers
             isa_check.check_no_scratch(os.path.join(objdir, 'mesh.o'), 'mc_[a-z_]*_kernel', strict=strict)
+            # mesh rendering: the triangle's nine coordinates, ten plane coefficients and box stay in registers across the views
+            isa_check.check_no_scratch(os.path.join(objdir, 'meshrender.o'), 'mesh_render_kernel', strict=strict)
             # plane-sweep warp: the window kernel walks the depth axis at the register limit of 4 waves per SIMD; what it keeps
             # across the walk must stay in registers
             isa_check.check_no_scratch(os.path.join(objdir, 'psv_variance.o'), 'psv_variance_window_kernel', strict=strict)

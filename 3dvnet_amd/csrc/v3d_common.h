@@ -54,6 +54,7 @@ enum Option {
   kOptGemmRounds,      // "gemm_rounds": 1 gather-GEMM in rounds for small M, 0 the one-step kernel
   kOptGemmPipe,        // "gemm_pipe": 1 sparse convolutions on the loader / matrix pipeline kernel, 0 the rounds kernel
   kOptPsvWalk,         // "psv_walk": plane chunks a wave of the window kernel walks: 0 auto (by shape), N = N chunks (bit-identical)
+  kOptRenderCoop,      // "render_coop": bounding boxes of more than this many pixels are rasterised by the whole wave (bit-identical)
   kOptCount
 };
 int option(Option o);

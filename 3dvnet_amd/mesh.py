@@ -5,7 +5,9 @@
   * ``extract``         volume (+ colour volume) -> vertices, colours, triangles as device tensors;
   * ``TriangleMesh``    a plain holder of those tensors with ``write_ply``;
   * ``read_ply_points`` reads the vertices of a file ``write_ply`` wrote (the reference's ``o3d.io.write_triangle_mesh`` /
-                        ``read_point_cloud`` round trip; both run on the host).
+                        ``read_point_cloud`` round trip; both run on the host);
+  * ``read_triangle_mesh``  reads a binary triangle-mesh PLY of someone else's making (ScanNet's ``*_vh_clean_2.ply``, the
+                        file ``scene_info['gt_mesh']`` names; the reference's ``o3d.io.read_triangle_mesh``) on the host.
 
 The triangulation is this project's own rule (``scripts/gen_mc_table.py``), not skimage's Lewiner tables: the vertex SET -- one
 vertex per sign-changing grid edge, which is all the 3D metrics read -- is defined by the volume alone, the triangles between
@@ -145,3 +147,84 @@ def read_ply(path):
 def read_ply_points(path):
     """The vertices of a file ``write_ply`` wrote, [V, 3] float64 (the reference's ``o3d.io.read_point_cloud(path).points``)."""
     return read_ply(path)[0]
+
+
+_PLY_SCALARS = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': '<i2', 'int16': '<i2', 'ushort': '<u2',
+                'uint16': '<u2', 'int': '<i4', 'int32': '<i4', 'uint': '<u4', 'uint32': '<u4', 'float': '<f4', 'float32': '<f4',
+                'double': '<f8', 'float64': '<f8'}
+
+
+def read_triangle_mesh(path):
+    """A binary little-endian PLY triangle mesh -> ``TriangleMesh`` on the host (vertices fp32, triangles int32, colours uint8
+    or None).  Accepted: a ``vertex`` element with ``float`` or ``double`` ``x y z`` and any further scalar properties (skipped,
+    except ``red green blue`` as ``uchar``, which are kept), followed by a ``face`` element whose only property is a list of
+    ``uchar`` count and ``int`` / ``uint`` indices, every face a triangle -- the layout of ScanNet's ``*_vh_clean_2.ply`` and
+    of ``write_ply``.  Anything else raises ``ValueError`` with the reason."""
+    with open(path, 'rb') as f:
+        data = f.read()
+
+    def bad(why):
+        return ValueError('read_triangle_mesh: %s: %s' % (path, why))
+
+    mark = data.find(b'end_header')
+    if not data.startswith(b'ply') or mark < 0:
+        raise bad('not a PLY file (no "ply" ... "end_header")')
+    end = data.find(b'\n', mark)
+    if end < 0:
+        raise bad('the header does not end with a newline')
+    end += 1
+    try:
+        lines = [ln.strip() for ln in data[:mark].decode('ascii').splitlines()]
+    except UnicodeDecodeError:
+        raise bad('the header is not ASCII')
+    lines = [ln for ln in lines[1:] if ln and not ln.startswith(('comment', 'obj_info'))]
+    if not lines or lines[0].split() != ['format', 'binary_little_endian', '1.0']:
+        raise bad('only "format binary_little_endian 1.0" is read, the file says %r' % (lines[0] if lines else ''))
+    elements = []                                   # [name, count, [property words]]
+    for ln in lines[1:]:
+        w = ln.split()
+        if w[0] == 'element' and len(w) == 3 and w[2].isdigit():
+            elements.append([w[1], int(w[2]), []])
+        elif w[0] == 'property' and elements and len(w) >= 3:
+            elements[-1][2].append(w[1:])
+        else:
+            raise bad('header line %r' % ln)
+    if [e[0] for e in elements[:2]] != ['vertex', 'face']:
+        raise bad('the elements must start with vertex, face; found %s' % [e[0] for e in elements])
+    if any(e[1] for e in elements[2:]):
+        raise bad('elements after the faces are not read (%s)' % [e[0] for e in elements[2:]])
+    (_, n_v, vprops), (_, n_f, fprops) = elements[:2]
+    fields = []
+    for w in vprops:
+        if w[0] == 'list' or len(w) != 2 or w[0] not in _PLY_SCALARS:
+            raise bad('vertex property %r (scalar properties only)' % ' '.join(w))
+        fields.append((w[1], _PLY_SCALARS[w[0]]))
+    names = [n for n, _ in fields]
+    if len(set(names)) != len(names):
+        raise bad('a vertex property is declared twice')
+    for axis in 'xyz':
+        if axis not in names or dict(fields)[axis] not in ('<f4', '<f8'):
+            raise bad('vertex property %s must be float or double' % axis)
+    if len(fprops) != 1 or fprops[0][0] != 'list' or len(fprops[0]) != 4:
+        raise bad('the face element must hold one list property, found %s' % [' '.join(w) for w in fprops])
+    _, count_t, index_t, _ = fprops[0]
+    if _PLY_SCALARS.get(count_t) != 'u1' or _PLY_SCALARS.get(index_t) not in ('<i4', '<u4'):
+        raise bad('face list of %s count and %s indices (uchar count with int or uint indices only)' % (count_t, index_t))
+    vt = np.dtype(fields)
+    ft = np.dtype([('n', 'u1'), ('i', _PLY_SCALARS[index_t], (3,))])
+    need = end + n_v * vt.itemsize + n_f * ft.itemsize
+    if len(data) != need:
+        raise bad('truncated, or a face that is not a triangle (%d bytes, %d expected for triangles)' % (len(data), need))
+    rows = np.frombuffer(data, dtype=vt, count=n_v, offset=end)
+    faces = np.frombuffer(data, dtype=ft, count=n_f, offset=end + n_v * vt.itemsize)
+    if n_f and not (faces['n'] == 3).all():
+        raise bad('a face that is not a triangle')
+    idx = faces['i']
+    if n_f and (int(idx.max()) >= 2 ** 31 or int(idx.min()) < 0 or int(idx.max()) >= n_v):
+        raise bad('a face index outside the %d vertices' % n_v)
+    verts = np.stack((rows['x'], rows['y'], rows['z']), axis=1).astype(np.float32).reshape(-1, 3)
+    cols = None
+    if all(c in names and dict(fields)[c] == 'u1' for c in ('red', 'green', 'blue')):
+        cols = torch.from_numpy(np.ascontiguousarray(np.stack((rows['red'], rows['green'], rows['blue']), axis=1).reshape(-1, 3)))
+    return TriangleMesh(torch.from_numpy(np.ascontiguousarray(verts)),
+                        torch.from_numpy(np.ascontiguousarray(idx.astype(np.int32).reshape(-1, 3))), cols)

@@ -20,7 +20,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib, fusion
+from . import _lib, fusion, meshtodepth
 
 KEYS = ('acc', 'comp', 'prec', 'recal', 'fscore')
 _STATUS = {1: 'the cloud holds a non-finite coordinate', 2: 'extent / voxel_size reaches 2^21 cells on an axis',
@@ -169,19 +169,23 @@ def eval_mesh(pcd_pred, pcd_trgt, threshold=.05, device=None):
 
 
 def depth_3d_metrics(preds, images, gt_points, z_thresh, n_consistent_thresh=3, voxel_downsample=0.02, dist_thresh=0.05,
-                     out_size=None, device=None):
-    """The chain of processresults.py:218-291 without files, GT-mesh masking or fusibile: ``fusion.prepare_preds`` ->
+                     out_size=None, device=None, gt_mesh=None):
+    """The chain of processresults.py:218-291 without files or fusibile: ``fusion.prepare_preds`` (-> with ``gt_mesh``, the
+    depths zeroed where that mesh, rendered from the same cameras at the fused size, is not seen: :262-266) ->
     ``fuse_depth_maps(trim=False)`` -> down-sample of the fused cloud (colours / 255 as attributes) and of ``gt_points``
     -> nearest neighbours in both directions -> metrics.  ``preds`` is a ``preds.npz`` path or mapping, ``images``
     [N, H, W, 3] at the fused size, ``gt_points`` [n, 3].  -> dict of the five metrics and ``'n'`` (the number of views).
 
     The points never leave the device.  Read-backs: 3 -- the two down-sampled counts (4 bytes each, they size the
-    neighbour searches) and the final 40-byte record."""
+    neighbour searches) and the final 40-byte record; with ``gt_mesh`` the renderer's status word as well."""
     _lib.load()
     dev = fusion._device(device)
     depths, poses, K = fusion.prepare_preds(preds, out_size)
     images = torch.as_tensor(images).to(dev)
-    pts, rgb, _, count = fusion.fuse_depth_maps(torch.from_numpy(depths).to(dev), torch.from_numpy(poses),
+    depths = torch.from_numpy(depths).to(dev)
+    if gt_mesh is not None:
+        depths = meshtodepth.mask_with_mesh(depths, gt_mesh, poses, K, device=dev)
+    pts, rgb, _, count = fusion.fuse_depth_maps(depths, torch.from_numpy(poses),
                                                 torch.from_numpy(K), images, z_thresh, n_consistent_thresh, trim=False)
     pred, _, n_pred = voxel_down_sample(pts, voxel_downsample, attr=rgb.float() / 255., count=count)
     gt = _to_device(_points(gt_points), dev)

@@ -11,10 +11,16 @@ volume with weights and colours (``mv3d/eval/tsdf_atlas.py``: ``TSDFFusion`` :34
   * ``fuse_preds_tsdf``      from a ``preds.npz`` record (path or mapping) to the ``TSDF``;
   * ``TSDF.get_mesh``        the volume -> a ``mesh.TriangleMesh`` on the device (``csrc/mesh.hip``: marching cubes with the
                              project's own case table and the reference's rules around it, tsdf_atlas.py:161-253);
-  * ``tsdf_mesh_metrics``    the rest of the ``run_tsdf`` branch (:383-397): mesh -> vertices -> down-sample -> 3D metrics.
+  * ``tsdf_mesh_metrics``    the rest of the ``run_tsdf`` branch (:383-397): mesh -> vertices -> down-sample -> 3D metrics;
+  * ``trim_mesh``            a mesh cut down to what given cameras saw (:71-150): rendered into every view
+                             (``meshtodepth``), the renderings integrated into a fresh volume, that volume meshed;
+  * ``mesh_3d_metrics``      the body of ``process_volume_3d_metrics`` (:172-200): trim, down-sample, 3D metrics.
 
-There is no CPU fallback: without the library or a HIP device every integrating or meshing entry raises ``V3DLibraryError``.
-``TSDF.transform``, the label volume, ``trim_mesh`` and ``MASK_USING_GT_MESH`` are not provided.
+``gt_mesh`` / ``mask_mesh`` arguments are the reference's ``MASK_USING_GT_MESH`` switch: depths are zeroed where a rendering of
+that mesh sees nothing (``meshtodepth.mask_with_mesh``).
+
+There is no CPU fallback: without the library or a HIP device every integrating, meshing or rendering entry raises
+``V3DLibraryError``.  ``TSDF.transform`` and the label volume are not provided.
 """
 import ctypes
 
@@ -25,6 +31,7 @@ import torch.nn.functional as F
 from . import _lib
 from . import fusion as _fusion
 from . import mesh as _mesh
+from . import meshtodepth as _meshtodepth
 from . import metrics3d as _metrics3d
 
 
@@ -265,41 +272,32 @@ def prepare_preds_tsdf(preds, images):
 
 
 def fuse_preds_tsdf(preds, images, vox_res=.04, trunc_ratio=3, vol_prcnt=.995, vol_margin=1.5, img_batch=100, color=True,
-                    device=None, return_fusion=False):
+                    device=None, return_fusion=False, gt_mesh=None):
     """The ``run_tsdf`` branch up to ``get_tsdf()``: bounds from ``volume_bounds``, one ``integrate_batch`` per chunk of
-    ``img_batch`` views, ``get_tsdf()``.  -> ``TSDF`` (on the device); ``return_fusion=True`` -> ``(TSDF, TSDFFusion)``."""
+    ``img_batch`` views, ``get_tsdf()``.  -> ``TSDF`` (on the device); ``return_fusion=True`` -> ``(TSDF, TSDFFusion)``.
+    ``gt_mesh``: each chunk's depths are masked with that mesh rendered at the predictions' size before they are integrated
+    (:368-371); the bounds are taken from the unmasked depths, as the reference takes them."""
     _lib.load()
     dev = _fusion._device(device)
     depths, poses, K, images = prepare_preds_tsdf(preds, images)
     origin, _, vol_dim = volume_bounds(depths.to(dev), K, poses, vol_prcnt, vol_margin, vox_res, img_batch)
     fus = TSDFFusion(vol_dim, vox_res, origin, trunc_ratio, dev, color=color, label=False)
+    masker = None if gt_mesh is None else _meshtodepth.Renderer(gt_mesh, depths.shape[1], depths.shape[2], device=dev)
     for start in range(0, depths.shape[0], int(img_batch)):
         sl = slice(start, start + int(img_batch))
-        fus.integrate_batch(projection_matrices(K[sl], poses[sl]), depths[sl], images[sl] if color else None)
+        d = depths[sl] if masker is None else _meshtodepth.mask_with_mesh(depths[sl], masker, poses[sl], K[sl])
+        fus.integrate_batch(projection_matrices(K[sl], poses[sl]), d, images[sl] if color else None)
     tsdf = fus.get_tsdf()
     return (tsdf, fus) if return_fusion else tsdf
 
 
-def tsdf_mesh_metrics(preds, images, gt_points, vox_res=.04, trunc_ratio=3, voxel_downsample=0.02, dist_thresh=0.05,
-                      vol_prcnt=.995, vol_margin=1.5, img_batch=100, device=None, return_mesh=False):
-    """The ``run_tsdf`` branch to its end (processresults.py:297-397) without files or GT-mesh masking: ``fuse_preds_tsdf``
-    -> ``get_mesh`` -> the mesh's vertices through ``metrics3d.voxel_down_sample`` -> ``metrics3d.eval_clouds`` against the
-    down-sampled ``gt_points`` [n, 3].  -> the dict of the five metrics and ``'n'`` (the number of views);
-    ``return_mesh=True`` -> ``(dict, TriangleMesh)``.  An empty mesh or ground truth gives NaN metrics, as the reference's
-    NumPy means do.  The vertices never leave the device; read-backs: the mesh's two counts, the two down-sampled counts and
-    the final 40-byte record."""
-    _lib.load()
-    dev = _fusion._device(device)
-    if isinstance(preds, (str, bytes)) or hasattr(preds, '__fspath__'):
-        with np.load(preds) as f:
-            preds = {k: f[k] for k in f.files}
-    n_views = int(np.asarray(preds['depth_preds']).shape[0])
-    tsdf = fuse_preds_tsdf(preds, images, vox_res, trunc_ratio, vol_prcnt, vol_margin, img_batch, color=True, device=dev)
-    mesh = tsdf.get_mesh()
+def _vertex_metrics(vertices, gt_points, voxel_downsample, dist_thresh, dev):
+    """A mesh's vertices [V, 3] (device) against ``gt_points``: both down-sampled, then ``metrics3d.eval_clouds`` -> dict of
+    the five metrics (NaN when either side is empty, as the reference's NumPy means give)."""
     out = {k: float('nan') for k in _metrics3d.KEYS}
     gt = _metrics3d._to_device(_metrics3d._points(gt_points), dev)
-    if mesh.vertices.shape[0] > 0 and gt.shape[0] > 0:
-        pred, _, n_pred = _metrics3d.voxel_down_sample(mesh.vertices, voxel_downsample)
+    if vertices.shape[0] > 0 and gt.shape[0] > 0:
+        pred, _, n_pred = _metrics3d.voxel_down_sample(vertices, voxel_downsample)
         trgt, _, n_trgt = _metrics3d.voxel_down_sample(gt, voxel_downsample)
         n_pred, n_trgt = int(n_pred.item()), int(n_trgt.item())
         for c in (n_pred, n_trgt):
@@ -307,5 +305,66 @@ def tsdf_mesh_metrics(preds, images, gt_points, vox_res=.04, trunc_ratio=3, voxe
                 _metrics3d._raise_status(-c)
         if n_pred > 0 and n_trgt > 0:
             out = dict(zip(_metrics3d.KEYS, _metrics3d.eval_clouds(pred[:n_pred], trgt[:n_trgt], dist_thresh).cpu().tolist()))
+    return out
+
+
+def tsdf_mesh_metrics(preds, images, gt_points, vox_res=.04, trunc_ratio=3, voxel_downsample=0.02, dist_thresh=0.05,
+                      vol_prcnt=.995, vol_margin=1.5, img_batch=100, device=None, return_mesh=False, gt_mesh=None):
+    """The ``run_tsdf`` branch to its end (processresults.py:297-397) without files: ``fuse_preds_tsdf`` (with ``gt_mesh``: the
+    predictions masked by that mesh) -> ``get_mesh`` -> the mesh's vertices through ``metrics3d.voxel_down_sample`` ->
+    ``metrics3d.eval_clouds`` against the down-sampled ``gt_points`` [n, 3].  -> the dict of the five metrics and ``'n'`` (the
+    number of views); ``return_mesh=True`` -> ``(dict, TriangleMesh)``.  An empty mesh or ground truth gives NaN metrics, as
+    the reference's NumPy means do.  The vertices never leave the device; read-backs: the mesh's two counts, the two
+    down-sampled counts and the final 40-byte record (and one status word per rendered chunk with ``gt_mesh``)."""
+    _lib.load()
+    dev = _fusion._device(device)
+    if isinstance(preds, (str, bytes)) or hasattr(preds, '__fspath__'):
+        with np.load(preds) as f:
+            preds = {k: f[k] for k in f.files}
+    n_views = int(np.asarray(preds['depth_preds']).shape[0])
+    tsdf = fuse_preds_tsdf(preds, images, vox_res, trunc_ratio, vol_prcnt, vol_margin, img_batch, color=True, device=dev,
+                           gt_mesh=gt_mesh)
+    mesh = tsdf.get_mesh()
+    out = _vertex_metrics(mesh.vertices, gt_points, voxel_downsample, dist_thresh, dev)
     out['n'] = n_views
     return (out, mesh) if return_mesh else out
+
+
+def trim_mesh(mesh, poses, K, images=None, size=(480, 640), mask_mesh=None, vox_res=.04, trunc_ratio=3, vol_prcnt=.995,
+              vol_margin=1.5, img_batch=100, device=None):
+    """The reference's ``trim_mesh`` (processresults.py:71-150) over given cameras -- ``poses`` [N, 4, 4] world -> camera, ``K``
+    [N, 3, 3] at ``size``: (1) ``meshtodepth.process_scene`` renders the mesh into every view; (2) ``volume_bounds`` of those
+    depths; (3) the depths -- with ``mask_mesh`` zeroed where a rendering of that mesh sees nothing (:134-137) -- go into a
+    ``TSDFFusion`` in chunks of ``img_batch``, with ``images`` [N, 3, h, w] fp32 as colours (None: a volume without colour);
+    (4) ``get_tsdf().get_mesh()``.  -> ``mesh.TriangleMesh`` on the device: the part of the surface the cameras saw."""
+    _lib.load()
+    dev = _fusion._device(device)
+    K, poses = torch.as_tensor(K).float().cpu(), torch.as_tensor(poses).float().cpu()
+    n, step = int(poses.shape[0]), int(img_batch)
+    if images is not None:
+        images = torch.as_tensor(images)
+        if tuple(images.shape) != (n, 3, int(size[0]), int(size[1])):
+            raise ValueError('trim_mesh: images must be [N, 3, h, w] = %s, got %s'
+                             % ((n, 3, int(size[0]), int(size[1])), tuple(images.shape)))
+    renderer = _meshtodepth.Renderer(mesh, size[0], size[1], device=dev)
+    depths = torch.cat([renderer.render(K[i:i + step], poses[i:i + step]) for i in range(0, n, step)], dim=0)
+    origin, _, vol_dim = volume_bounds(depths, K, poses, vol_prcnt, vol_margin, vox_res, img_batch)
+    fus = TSDFFusion(vol_dim, vox_res, origin, trunc_ratio, dev, color=images is not None, label=False)
+    masker = None if mask_mesh is None else _meshtodepth.Renderer(mask_mesh, size[0], size[1], device=dev)
+    for i in range(0, n, step):
+        sl = slice(i, i + step)
+        d = depths[sl] if masker is None else _meshtodepth.mask_with_mesh(depths[sl], masker, poses[sl], K[sl])
+        fus.integrate_batch(projection_matrices(K[sl], poses[sl]), d, None if images is None else images[sl])
+    return fus.get_tsdf().get_mesh()
+
+
+def mesh_3d_metrics(mesh, gt_points, poses, K, images=None, size=(480, 640), mask_mesh=None, vox_res=.04, trunc_ratio=3,
+                    voxel_downsample=0.02, dist_thresh=0.05, vol_prcnt=.995, vol_margin=1.5, img_batch=100, device=None,
+                    return_mesh=False):
+    """The body of ``process_volume_3d_metrics`` (processresults.py:172-200) without files: ``trim_mesh``, then the trimmed
+    mesh's vertices and ``gt_points`` down-sampled and scored by ``metrics3d.eval_clouds``.  -> the dict of the five metrics;
+    ``return_mesh=True`` -> ``(dict, trimmed TriangleMesh)``."""
+    dev = _fusion._device(device)
+    trimmed = trim_mesh(mesh, poses, K, images, size, mask_mesh, vox_res, trunc_ratio, vol_prcnt, vol_margin, img_batch, dev)
+    out = _vertex_metrics(trimmed.vertices, gt_points, voxel_downsample, dist_thresh, dev)
+    return (out, trimmed) if return_mesh else out

@@ -55,8 +55,11 @@ extern "C" {
  *   "gemm_rounds"     1 | 0      gather-GEMM in rounds for small M | the one-step kernel (bit-identical)
  *   "gemm_pipe"       1 | 0      sparse convolutions on the loader / matrix pipeline kernel | the rounds kernel (bit-identical)
  *   "psv_walk"        0 | N      plane chunks (of 8 planes) a wave of the window warp kernel walks: chosen from the shape | N (bit-identical)
- * Unknown names, gemm_rounds / gemm_pipe values other than 0 and 1, and a negative psv_walk -> V3D_ERR_BAD_ARG.
- * ("psv_walk" is additive within ABI version 9: a new option name, no changed signature; v3d_version() is not bumped.) */
+ *   "render_coop"     N          v3d_mesh_render_depth_f32: bounding boxes of more than N pixels are rasterised by the whole wave,
+ *                                smaller ones by the triangle's own thread (default 64; 0 = every box; bit-identical)
+ * Unknown names, gemm_rounds / gemm_pipe values other than 0 and 1, and a negative psv_walk / render_coop -> V3D_ERR_BAD_ARG.
+ * ("psv_walk" and "render_coop" are additive within ABI version 9: new option names, no changed signature; v3d_version() is not
+ * bumped.) */
 int v3d_set_option(const char* name, int value);
 int v3d_get_option(const char* name, int* value);
 
@@ -597,6 +600,42 @@ int v3d_mesh_count_f32(const float* tsdf, int nx, int ny, int nz, int mode, int3
 int v3d_mesh_extract_f32(const float* tsdf, const float* color, int nx, int ny, int nz, double voxel_size,
                          const float* origin_host, int mode, float* verts, uint8_t* colors, int v_cap, int32_t* tris, int f_cap,
                          const void* workspace, size_t workspace_bytes, void* stream);
+
+/* Depth maps of a triangle mesh (csrc/meshrender.hip): what mv3d/eval/meshtodepth.py (Renderer / process_scene) gets from pyrender
+ * -- the depth of the nearest surface along the camera axis at every pixel, 0 where nothing is seen -- as a rasteriser with pinned
+ * fp32 arithmetic.  ABI version: STILL 9 (additive, as the TSDF and mesh symbols are).
+ *   Inputs (DEVICE): verts [n_vert, 3] fp32 world coordinates; tris [n_tri, 3] int32; projections [n_view, 12] fp32 = the 3 x 4
+ *   matrices K [R | t], row major (world -> camera poses, as v3d_tsdf_integrate_f32 takes them).  pixel_center, znear, zfar are
+ *   taken as fp32.  Output: depth [n_view, h, w] fp32; status: one int32 DEVICE word.
+ *   Pixel (r, c) samples the image-plane point (px, py) = (fl(c + pixel_center), fl(r + pixel_center)) in the coordinates of K
+ *   (u = fx X / Z + cx).  pixel_center = 0.5 is OpenGL's sample position, 0 the integer-centre convention of the TSDF kernel.
+ *   Per view and triangle, all fp32, every operation rounded on its own (no contraction) except the projection chain:
+ *     q_i = P . [X_i; 1] for the three vertices, each row a k-ordered FMA chain whose homogeneous term is a rounded addition (the
+ *           function of v3d_tsdf_integrate_f32); q_i.z is the camera depth of the vertex;
+ *     A_0 = q_1 x q_2, A_1 = q_2 x q_0, A_2 = q_0 x q_1, each component fl(fl(a b) - fl(c d)) in the usual order
+ *           (y z' - z y', z x' - x z', x y' - y x');
+ *     det = fl(fl(fl(q_0.x A_0.x) + fl(q_0.y A_0.y)) + fl(q_0.z A_0.z));
+ *     per pixel e_i = fl(fl(fl(A_i.x px) + fl(A_i.y py)) + A_i.z), s = fl(fl(e_0 + e_1) + e_2);
+ *     the pixel has a fragment iff (e_0 >= 0 and e_1 >= 0 and e_2 >= 0 and s > 0) or (e_0 <= 0 and e_1 <= 0 and e_2 <= 0 and
+ *     s < 0), and z = det / s (IEEE division) satisfies znear <= z <= zfar (a NaN fails).
+ *   depth = the smallest z of any fragment at the pixel, 0 where there is none.  This is homogeneous rasterisation: both sides of a
+ *   triangle are seen; a triangle that crosses the near plane or the camera plane needs no geometric clipping (the range test is
+ *   the clip, per fragment); the inclusive edge rule leaves no crack along a shared edge.  Coverage is this predicate, whatever
+ *   way the kernel walks the image, with two rejections that exact arithmetic implies and the kernel takes on the fp32 values: a
+ *   triangle whose three q_i.z are all < znear has no fragment (z is a convex combination of them), and a triangle whose three
+ *   q_i.z are all >= znear has none outside the bounding box of its three (q.x / q.z, q.y / q.z) widened by one pixel.
+ *   Skipped triangles: one with an index outside [0, n_vert) sets bit value 1 of *status, one with a non-finite vertex coordinate
+ *   bit value 2; the other triangles are rendered as if those were absent.  *status is 0 after a clean call.
+ * The minimum is taken on the bits of z (positive floats order as their bit patterns) with 32-bit atomics, so the output does not
+ * depend on scheduling: repeated calls, n views in one call or n calls of one view, and any "render_coop" give identical bits.
+ * Asynchronous on `stream`; no workspace, no allocation, no synchronisation.  Host-side errors: V3D_ERR_BAD_ARG for a null
+ * pointer, a parameter that is not finite, znear outside (0, zfar); V3D_ERR_BAD_SHAPE for a count or size that is not positive or
+ * n_view h w >= 2^31. */
+#define V3D_RENDER_STATUS_BAD_INDEX 1
+#define V3D_RENDER_STATUS_NON_FINITE 2
+int v3d_mesh_render_depth_f32(const float* verts, int n_vert, const int32_t* tris, int n_tri, const float* projections, int n_view,
+                              int h, int w, double pixel_center, double znear, double zfar, float* depth, int32_t* status,
+                              void* stream);
 
 #ifdef __cplusplus
 }

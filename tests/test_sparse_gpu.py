@@ -1,0 +1,682 @@
+"""The sparse-structure kernels per element, through the C ABI, against tests/sparse_oracle.py (a Python dict and an fp32 chain
+restated in NumPy; tests/test_sparse_oracle.py pins it on the CPU):
+
+  * hash table + 27-offset neighbour tables (csrc/sparse_hash.h, csrc/sparse.hip): exact equality, at the capacity steps, with
+    batch ids 0 / 1 / 65535, coordinates -8 and 65519 on every axis, a full 12^3 block, and probe chains that wrap past the last slot;
+  * the key helpers of csrc/voxelize.hip (sort/unique, lower bound, strided keys, unpack): exact equality, unsigned order of keys with
+    bit 63 set, true floor below zero;
+  * v3d_sparse_interp_f32 itself: bit equality where the arithmetic is exact, |out - ref64| <= 9 u S everywhere else (u = 2^-24,
+    S = sum_k |w_k f_k|; derivation in sparse_oracle.py), exact zeros where no corner is present, every channel count and the
+    wide-row layout of the decoder;
+  * the corner table of the fused decoder (csrc/decoder.hip) against the unfused chain at the same edges.
+
+No number here comes from the kernels under test.  Every case that its inputs could make vacuous asserts that they do not.
+
+Wrong variants of the library these tests were tried against (none committed), and what caught each: probe chains that stop at the
+table end instead of wrapping -> test_probe_chains_wrap_past_the_last_slot; the corner ROW taken with the x and y corner bits
+swapped while the weight keeps them -> the bit-exact, generic, away and decoder tests; a gather that writes one column too many ->
+test_interp_channel_counts_and_wide_row_layout (every C); truncation for floor in strided_keys_kernel ->
+test_strided_keys_sort_unpack_equal_floor_division (every ts).  Swapping the two bits for row AND weight alike only renumbers the
+corners: the same 8 terms, and rightly no failure.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import sparse_oracle as so
+from conftest import v3d
+
+pytestmark = pytest.mark.gpu
+
+OK, BAD_SHAPE, BAD_ARG, WS_SMALL, UNSUPPORTED = 0, -1, -2, -3, -5           # include/v3d.h
+BATCHES = np.array([0, 1, 65535])
+EXTREME = [(65535, -8, 65519, -8), (65535, 65519, -8, 65519), (0, -8, 5, 5), (0, 5, -8, 5), (0, 5, 5, -8),
+           (1, 65519, 3, 3), (1, 3, 65519, 3), (1, 3, 3, 65519)]
+SENTINEL = 0x7fc12345                                                       # a NaN with a payload: any write shows
+
+
+def _libs():
+    libm = v3d('_lib')
+    return libm, libm.load()
+
+
+def _to(a, cuda, dtype):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).to(cuda).contiguous()
+
+
+def _build(coords, cuda):
+    """v3d_hash_build on int32 [n, 4] -> (device coords, table buffer)."""
+    libm, lib = _libs()
+    c = _to(coords, cuda, torch.int32)
+    n = c.shape[0]
+    nbytes = lib.v3d_hash_bytes(n)
+    assert nbytes == so.table_capacity(n) * 16 + 16
+    table = torch.empty(nbytes, dtype=torch.uint8, device=cuda)
+    assert lib.v3d_hash_build(c.data_ptr(), n, table.data_ptr(), nbytes, libm.stream_ptr(cuda)) == OK
+    return c, table
+
+
+def _status(table, n, cuda):
+    libm, lib = _libs()
+    return lib.v3d_hash_status(table.data_ptr(), n, libm.stream_ptr(cuda))
+
+
+def _neighbours(table, n_in, out_coords, step, cuda):
+    libm, lib = _libs()
+    oc = out_coords if torch.is_tensor(out_coords) else _to(out_coords, cuda, torch.int32)
+    n_out = oc.shape[0]
+    nbr = torch.empty((27, n_out), dtype=torch.int32, device=cuda)
+    nbr.fill_(-7)
+    assert lib.v3d_sparse_neighbors(table.data_ptr(), n_in, oc.data_ptr(), n_out, step, nbr.data_ptr(), libm.stream_ptr(cuda)) == OK
+    return nbr.cpu().numpy().astype(np.int64)
+
+
+def _block(side, lo, ts=1, batches=BATCHES):
+    g = np.stack(np.meshgrid(np.arange(len(batches)), np.arange(side), np.arange(side), np.arange(side), indexing='ij'), -1)
+    g = g.reshape(-1, 4)
+    return np.concatenate((np.asarray(batches)[g[:, :1]], (g[:, 1:] + lo) * ts), axis=1).astype(np.int64)
+
+
+def _edge_map(n, seed, fill=0.35):
+    """n unique rows in shuffled order: the extreme rows (-8 and 65519 on every axis, batch 65535) first in line, the rest a random
+    ``fill`` of a block that starts at -8 in the batches 0 / 1 / 65535."""
+    rng = np.random.default_rng(seed)
+    ext = np.array(EXTREME[:min(n, len(EXTREME))], dtype=np.int64)
+    m = n - ext.shape[0]
+    rows = ext
+    if m > 0:
+        side = max(3, int(np.ceil((m / 3 / fill) ** (1 / 3))))
+        blk = _block(side, -8)
+        taken = set(map(tuple, ext.tolist()))
+        blk = blk[[tuple(r) not in taken for r in blk.tolist()]]
+        rows = np.concatenate((ext, blk[rng.choice(blk.shape[0], m, replace=False)]))
+    assert rows.shape[0] == n and np.unique(rows, axis=0).shape[0] == n
+    return rows[rng.permutation(n)]
+
+
+# ---- hash table and neighbour tables --------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize('n', [1, 15, 16, 17, 4096, 4097, 20000])
+def test_hash_finds_every_row_and_neighbours_are_exact(n, cuda):
+    """Row counts on both sides of the capacity steps (capacity = smallest power of two >= 4 n, at least 64).  The rows at -8 and
+    65519 are FOUND (status clean, centre column = own row); the probes one voxel beyond them give -1 -- a key that wrapped into
+    another field would find somebody else's row."""
+    coords = _edge_map(n, seed=n)
+    assert so.table_capacity(n) in (64, 128, 16384, 32768, 131072)
+    assert set(np.unique(coords[:, 0])) <= {0, 1, 65535} and (n < 8 or len(np.unique(coords[:, 0])) == 3)
+    for ax in (1, 2, 3):
+        assert n < 8 or ((coords[:, ax] == -8).any() and (coords[:, ax] == so.COORD_MAX).any())
+    assert coords.min() == -8 and coords[:, 1:].max() == so.COORD_MAX
+    c, table = _build(coords, cuda)
+    assert _status(table, n, cuda) == OK
+    nbr = _neighbours(table, n, c, 1, cuda)
+    ref = so.neighbours(coords, coords, 1)
+    assert np.array_equal(nbr, ref)
+    assert np.array_equal(nbr[13], np.arange(n))                                 # the centre column is the identity
+    ext = np.nonzero((coords[:, 1:] == -8).any(axis=1) | (coords[:, 1:] == so.COORD_MAX).any(axis=1))[0]
+    assert ext.size >= min(n, 8) and np.array_equal(nbr[13, ext], ext)           # the extreme rows are found
+    beyond = np.zeros((27, n), dtype=bool)
+    for k, o in enumerate(so.offsets()):
+        q = coords[:, 1:] + o
+        beyond[k] = ((q < -8) | (q > so.COORD_MAX)).any(axis=1)
+    assert beyond[:, ext].any() and (nbr[beyond] == -1).all()                    # one voxel beyond the key range: nothing
+    if n >= 4096:
+        off = np.delete(nbr, 13, axis=0)
+        assert (off >= 0).mean() > 0.1 and (off < 0).mean() > 0.1                # hits and misses both occur
+
+
+@pytest.mark.parametrize('step', [1, 2, 4, -2, -4])
+def test_neighbour_steps_on_the_map_itself(step, cuda):
+    coords = _edge_map(3000, seed=50, fill=0.6)
+    c, table = _build(coords, cuda)
+    assert _status(table, 3000, cuda) == OK
+    nbr = _neighbours(table, 3000, c, step, cuda)
+    ref = so.neighbours(coords, coords, step)
+    assert np.array_equal(nbr, ref)
+    assert np.array_equal(nbr[13], np.arange(3000))
+    off = np.delete(ref, 13, axis=0)
+    assert (off >= 0).sum() > 3000 and (off < 0).sum() > 3000
+    # a probe below -8 or above 65519 leaves the key range in both directions of the step
+    assert (coords[:, 1:] + abs(step) > so.COORD_MAX).any() and (coords[:, 1:] - abs(step) < -8).any()
+
+
+@pytest.mark.parametrize('ts', [1, 2])
+def test_neighbours_of_stride2_and_transposed_patterns(ts, cuda):
+    """The two tables of a U-Net level pair: fine table probed from the coarse coordinates with step +ts (stride-2 convolution),
+    coarse table probed from the fine coordinates with step -ts (transposed convolution)."""
+    rng = np.random.default_rng(60 + ts)
+    blk = _block(14, -8 // ts, ts)
+    fine = blk[rng.choice(blk.shape[0], 2500, replace=False)]
+    coarse = so.strided_coords(fine, ts)
+    assert fine[:, 1:].min() == -8 and 200 < coarse.shape[0] < fine.shape[0]
+    cf, tf = _build(fine, cuda)
+    cc, tc = _build(coarse, cuda)
+    assert _status(tf, fine.shape[0], cuda) == OK and _status(tc, coarse.shape[0], cuda) == OK
+    down = _neighbours(tf, fine.shape[0], cc, ts, cuda)
+    ref = so.neighbours(fine, coarse, ts)
+    assert np.array_equal(down, ref) and (ref >= 0).sum() > coarse.shape[0] and (ref < 0).any()
+    up = _neighbours(tc, coarse.shape[0], cf, -ts, cuda)
+    ref = so.neighbours(coarse, fine, -ts)
+    assert np.array_equal(up, ref) and (ref < 0).any()
+    assert (ref >= 0).sum(axis=0).min() >= 1                                     # every fine voxel has its coarse parent
+
+
+def test_clustered_block_long_probe_chains(cuda):
+    """A full 12^3 block: packed keys that differ in a few low bits only.  Probed from the 14^3 grid around it, so that the shell
+    of absent coordinates runs each chain to its empty slot."""
+    rng = np.random.default_rng(70)
+    blk = _block(12, -7, batches=[0])
+    blk = blk[rng.permutation(blk.shape[0])]
+    grid = _block(14, -8, batches=[0])
+    c, table = _build(blk, cuda)
+    assert _status(table, blk.shape[0], cuda) == OK
+    nbr = _neighbours(table, blk.shape[0], grid, 1, cuda)
+    ref = so.neighbours(blk, grid, 1)
+    assert np.array_equal(nbr, ref)
+    assert (ref[13] >= 0).sum() == 12 ** 3 and (ref[13] < 0).sum() == 14 ** 3 - 12 ** 3
+
+
+def test_probe_chains_wrap_past_the_last_slot(cuda):
+    """40 rows whose home slot lies in the last 4 of the 256 slots (chosen with the restated hash; the expectation is the dict's):
+    at least 36 of them sit at the front of the table, and absent keys with such a home slot walk the whole wrapped run."""
+    n, cap = 40, 256
+    assert so.table_capacity(n) == cap
+    rng = np.random.default_rng(80)
+    cand = _block(24, -8, batches=[0, 65535])
+    home = so.home_slot(cand, n)
+    last = cand[home >= cap - 4]
+    assert last.shape[0] >= 240
+    last = last[rng.permutation(last.shape[0])]
+    rows, absent = last[:n], last[n:n + 200]
+    assert (so.home_slot(rows, n) >= cap - 4).all() and rows.shape[0] > cap - int(so.home_slot(rows, n).min())   # more keys than slots left
+    c, table = _build(rows, cuda)
+    assert _status(table, n, cuda) == OK
+    others = cand[rng.choice(cand.shape[0], 300, replace=False)]
+    queries = np.concatenate((rows, absent, others))
+    nbr = _neighbours(table, n, queries, 1, cuda)
+    ref = so.neighbours(rows, queries, 1)
+    assert np.array_equal(nbr, ref)
+    assert np.array_equal(nbr[13, :n], np.arange(n)) and (nbr[13, n:n + 200] == -1).all()
+
+
+def test_structure_calls_reject_bad_arguments_before_any_launch(cuda):
+    libm, lib = _libs()
+    s = libm.stream_ptr(cuda)
+    coords = _edge_map(100, seed=90)
+    c, table = _build(coords, cuda)
+    oc = torch.zeros((101, 4), dtype=torch.int32, device=cuda)
+    oc[:100] = c
+    nbr = torch.full((27, 100), -7, dtype=torch.int32, device=cuda)
+    call = lambda ptr, n_out, step: lib.v3d_sparse_neighbors(table.data_ptr(), 100, ptr, n_out, step, nbr.data_ptr(), s)
+    assert call(oc.data_ptr(), 100, 0) == BAD_SHAPE
+    assert call(oc.data_ptr(), 0, 1) == BAD_SHAPE
+    assert oc.data_ptr() % 16 == 0 and call(oc.data_ptr() + 4, 100, 1) == BAD_ARG        # a coordinate row is read as one int4
+    assert b'16-byte aligned' in lib.v3d_last_error()
+    assert lib.v3d_sparse_neighbors(table.data_ptr(), 0, oc.data_ptr(), 100, 1, nbr.data_ptr(), s) == BAD_SHAPE
+    torch.cuda.synchronize()
+    assert (nbr == -7).all()
+    assert call(oc.data_ptr(), 100, 1) == OK                                          # and the same buffers do work
+    assert np.array_equal(nbr.cpu().numpy(), so.neighbours(coords, coords, 1))
+    # table build: empty map, buffer one byte short
+    nbytes = lib.v3d_hash_bytes(100)
+    buf = torch.full((nbytes,), 0x5a, dtype=torch.uint8, device=cuda)
+    assert lib.v3d_hash_build(c.data_ptr(), 0, buf.data_ptr(), nbytes, s) == BAD_SHAPE
+    assert lib.v3d_hash_build(c.data_ptr(), 100, buf.data_ptr(), nbytes - 1, s) == WS_SMALL
+    torch.cuda.synchronize()
+    assert (buf == 0x5a).all()
+
+
+# ---- key helpers ----------------------------------------------------------------------------------------------------------------
+
+def _sort_unique(keys, cuda):
+    libm, lib = _libs()
+    n = keys.shape[0]
+    k = _to(keys.view(np.int64), cuda, torch.int64)
+    out = torch.empty(n, dtype=torch.int64, device=cuda)
+    nbytes = lib.v3d_sort_unique_workspace_bytes(n)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=cuda)
+    cnt = ctypes.c_int(-1)
+    assert lib.v3d_sort_unique_u64(k.data_ptr(), n, out.data_ptr(), ctypes.byref(cnt), ws.data_ptr(), nbytes, libm.stream_ptr(cuda)) == OK
+    assert torch.equal(k.cpu(), torch.from_numpy(keys.view(np.int64)))           # the input is not sorted in place
+    return out[:cnt.value].cpu().numpy().view(np.uint64), (k, ws, nbytes)
+
+
+def _keys(n, kind, seed):
+    """uint64 keys: small values mixed with values whose bit 63 is set (as signed integers those sort FIRST)."""
+    rng = np.random.default_rng(seed)
+    big = np.uint64(1) << np.uint64(63)
+    if kind == 'equal':
+        return np.full(n, big | np.uint64(5), dtype=np.uint64)
+    distinct = n if kind == 'unique' else max(min(n, 2), n // 3)
+    v = rng.choice(1 << 22, distinct, replace=False).astype(np.uint64)
+    v[::2] |= big                                                                # every other value has bit 63 set
+    if distinct >= 3:
+        v[:3] = [0, np.iinfo(np.uint64).max - 1, big]
+    keys = v[rng.permutation(distinct)] if kind == 'unique' else v[rng.integers(0, distinct, n)]
+    if kind == 'dups' and n >= 2:
+        keys[:2] = v[:2]
+    return keys
+
+
+@pytest.mark.parametrize('kind', ['dups', 'unique', 'equal'])
+@pytest.mark.parametrize('n', [1, 2, 255, 256, 257, 100000])
+def test_sort_unique_u64_equals_numpy_unique(n, kind, cuda):
+    keys = _keys(n, kind, seed=n)
+    top = keys >> np.uint64(63) == 1
+    assert top.any() and (kind == 'equal' or n < 2 or (~top).any())              # bit-63 keys are present, mixed with small ones
+    ref = np.unique(keys)
+    assert {'equal': ref.size == 1, 'unique': ref.size == n, 'dups': n < 6 or ref.size < n}[kind]
+    got, _ = _sort_unique(keys, cuda)
+    assert got.shape == ref.shape and np.array_equal(got, ref)
+
+
+def test_sort_unique_rejects_bad_arguments(cuda):
+    libm, lib = _libs()
+    keys = _keys(300, 'dups', 1)
+    _, (k, ws, nbytes) = _sort_unique(keys, cuda)
+    out = torch.full((300,), -3, dtype=torch.int64, device=cuda)
+    cnt = ctypes.c_int(-1)
+    s = libm.stream_ptr(cuda)
+    assert lib.v3d_sort_unique_u64(k.data_ptr(), 0, out.data_ptr(), ctypes.byref(cnt), ws.data_ptr(), nbytes, s) == BAD_SHAPE
+    assert lib.v3d_sort_unique_u64(k.data_ptr(), 300, out.data_ptr(), ctypes.byref(cnt), ws.data_ptr(), nbytes - 1, s) == WS_SMALL
+    torch.cuda.synchronize()
+    assert cnt.value == -1 and (out == -3).all()
+
+
+@pytest.mark.parametrize('n_u', [1, 2, 1000])
+def test_lower_bound_u64_equals_searchsorted(n_u, cuda):
+    libm, lib = _libs()
+    rng = np.random.default_rng(100 + n_u)
+    big = np.uint64(1) << np.uint64(63)
+    u = (rng.choice(1 << 22, n_u, replace=False).astype(np.uint64) + np.uint64(10)) * np.uint64(4)
+    u[::2] |= big
+    u = np.unique(u)
+    assert u.size == n_u and u[0] > 0 and (u >> np.uint64(63) == 1).any()
+    q = np.concatenate((u, u - np.uint64(1), u + np.uint64(1), u[:1] - np.uint64(7), u[-1:] + np.uint64(9),
+                        np.array([0, np.iinfo(np.uint64).max, 5, int(big) - 1], dtype=np.uint64)))
+    q = q[rng.permutation(q.size)]
+    ref = np.searchsorted(u, q, side='left')
+    assert (ref == 0).any() and (ref == n_u).any()                               # below the first and above the last key
+    assert n_u < 3 or (~np.isin(q, u) & (ref > 0) & (ref < n_u)).any()           # absent keys in between
+    ud, qd = _to(u.view(np.int64), cuda, torch.int64), _to(q.view(np.int64), cuda, torch.int64)
+    out = torch.full((q.size,), -3, dtype=torch.int64, device=cuda)
+    assert lib.v3d_lower_bound_u64(ud.data_ptr(), n_u, qd.data_ptr(), q.size, out.data_ptr(), libm.stream_ptr(cuda)) == OK
+    assert np.array_equal(out.cpu().numpy(), ref)
+
+
+@pytest.mark.parametrize('ts', [1, 2, 4])
+def test_strided_keys_sort_unpack_equal_floor_division(ts, cuda):
+    """v3d_strided_keys -> v3d_sort_unique_u64 -> v3d_unpack_coords, and SparseUNet._strided_coords, on coordinates from -8 upward
+    in the batches 0 / 1 / 65535 (batch 65535 sets bit 63 of the key: it sorts last only in unsigned order)."""
+    libm, lib = _libs()
+    sm = v3d('scenemodeling')
+    rng = np.random.default_rng(110 + ts)
+    blk = _block(13, -8 // ts, ts)
+    coords = blk[rng.choice(blk.shape[0], 2000, replace=False)]
+    neg = coords[:, 1:][coords[:, 1:] < 0]
+    assert coords[:, 1:].min() == -8 and (neg % (2 * ts) != 0).any()             # floor and truncation differ on these
+    assert (coords[:, 0] == 65535).any()
+    ref = so.strided_coords(coords, ts)
+    assert ref[:, 1:].min() == -8 and 100 < ref.shape[0] < 2000
+    c = _to(coords, cuda, torch.int32)
+    s = libm.stream_ptr(cuda)
+    keys = torch.empty(2000, dtype=torch.int64, device=cuda)
+    assert lib.v3d_strided_keys(c.data_ptr(), 2000, ts, keys.data_ptr(), s) == OK
+    uniq, _ = _sort_unique(keys.cpu().numpy().view(np.uint64), cuda)
+    ud = _to(uniq.view(np.int64), cuda, torch.int64)
+    out = torch.full((uniq.size, 4), -99, dtype=torch.int32, device=cuda)
+    assert lib.v3d_unpack_coords(ud.data_ptr(), uniq.size, out.data_ptr(), s) == OK
+    assert np.array_equal(out.cpu().numpy(), ref)
+    lv = sm.SparseLevel(c, ts)
+    assert np.array_equal(sm.SparseUNet._strided_coords(lv).cpu().numpy(), ref)
+    # bad shapes: nothing is written
+    assert lib.v3d_strided_keys(c.data_ptr(), 0, ts, keys.data_ptr(), s) == BAD_SHAPE
+    assert lib.v3d_strided_keys(c.data_ptr(), 2000, 0, keys.data_ptr(), s) == BAD_SHAPE
+    assert lib.v3d_unpack_coords(ud.data_ptr(), 0, out.data_ptr(), s) == BAD_SHAPE
+
+
+# ---- sparse trilinear interpolation ---------------------------------------------------------------------------------------------
+
+class _Interp:
+    """One hashed level on the device + v3d_sparse_interp_f32 into a sentinel-filled [n_q, ld_out] buffer."""
+
+    def __init__(self, coords, feats, ts, min_pts, res, cuda):
+        self.coords, self.feats, self.ts, self.min_pts, self.res, self.cuda = coords, feats, ts, min_pts, res, cuda
+        self.c, self.table = _build(coords, cuda)
+        assert _status(self.table, coords.shape[0], cuda) == OK
+        self.f = _to(feats, cuda, torch.float32)
+        self.mn = _to(min_pts, cuda, torch.float32)
+
+    def run(self, pts, pts_batch, n_hyp, ld_out=None, col0=0, n_pts=None, ws_short=0, C=None, expect=OK):
+        libm, lib = _libs()
+        pts = np.asarray(pts, dtype=np.float32).reshape(-1, n_hyp, 3)
+        pts_batch = np.asarray(pts_batch, dtype=np.int64)
+        assert pts_batch.shape[0] == pts.shape[0] and pts_batch.min() >= 0 and pts_batch.max() < self.min_pts.shape[0]
+        rows = pts.shape[0]
+        n_pts = rows if n_pts is None else n_pts
+        C = self.feats.shape[1] if C is None else C
+        ld = C if ld_out is None else ld_out
+        assert col0 + C <= ld and n_pts <= rows and C <= self.feats.shape[1]
+        out = torch.empty((rows * n_hyp, ld), dtype=torch.int32, device=self.cuda)
+        out.fill_(SENTINEL)
+        p, pb = _to(pts, self.cuda, torch.float32), _to(pts_batch, self.cuda, torch.int64)
+        nbytes = lib.v3d_sparse_interp_workspace_bytes(rows, n_hyp)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.cuda)
+        rc = lib.v3d_sparse_interp_f32(self.table.data_ptr(), self.coords.shape[0], self.f.data_ptr(), C, self.ts, p.data_ptr(),
+                                       pb.data_ptr(), n_pts, n_hyp, self.mn.data_ptr(), float(self.res), out.data_ptr(), ld, col0,
+                                       ws.data_ptr(), lib.v3d_sparse_interp_workspace_bytes(n_pts, n_hyp) - ws_short,
+                                       libm.stream_ptr(self.cuda))
+        assert rc == expect
+        return out.cpu().numpy()                                                 # int32 bit patterns
+
+    def ref(self, pts, pts_batch, n_hyp):
+        return so.interp(self.coords, self.feats, self.ts, pts, pts_batch, n_hyp, self.min_pts, self.res)
+
+    def corners(self, pts, pts_batch, n_hyp):
+        return so.corner_table(self.coords, self.ts, pts, pts_batch, n_hyp, self.min_pts, self.res)
+
+
+def _check_bound(bits, val, s, what):
+    """|out - ref64| <= 9 u S for EVERY element (S = 0: exact zero); prints and returns the worst ratio to the bound."""
+    out = bits.view(np.float32).astype(np.float64)
+    assert np.isfinite(out).all(), what
+    err = np.abs(out - val)
+    bad = err > so.INTERP_BOUND * s
+    m = s > 0
+    worst = float((err[m] / (so.INTERP_BOUND * s[m])).max()) if m.any() else 0.0
+    print('%s: worst |out - ref64| / (9 u S) = %.3f over %d elements (%d with S = 0)' % (what, worst, out.size, (~m).sum()))
+    assert not bad.any(), '%s: %d of %d elements outside 9 u S, worst ratio %.3f, first at %s' % (
+        what, bad.sum(), out.size, worst, np.argwhere(bad)[0])
+    return worst
+
+
+def _lattice_map(rng, side, lo, ts, fill, extra=()):
+    blk = _block(side, lo, ts, batches=[0, 1])
+    rows = blk[rng.random(blk.shape[0]) < fill]
+    extra = np.array([r for r in extra if tuple(r) not in set(map(tuple, rows.tolist()))], dtype=np.int64).reshape(-1, 4)
+    rows = np.concatenate((rows, extra))
+    return rows[rng.permutation(rows.shape[0])]
+
+
+@pytest.mark.parametrize('ts', [1, 2, 4])
+def test_interp_is_bit_exact_where_the_arithmetic_is(ts, cuda):
+    """res = 2^-4, min_pts multiples of res, queries at min + (i + j/4) res, integer features: qc = (i + j/4) ts, the weights are
+    multiples of 1/64 and every product and partial sum is exact in fp32 -- contraction or not.  Bit equality over the whole output;
+    the query set holds lattice points, face points, edge points and points below the level minimum."""
+    rng = np.random.default_rng(200 + ts)
+    res = 0.0625
+    coords = _lattice_map(rng, 4, 0, ts, 0.8, extra=[(0, -2 * ts, -2 * ts, -2 * ts), (1, -ts, 0, 0), (0, -2 * ts, 0, ts)])
+    feats = rng.integers(-8, 9, (coords.shape[0], 8)).astype(np.float32)
+    min_pts = np.array([[-1.25, 0.5, 3.0], [2.0, -0.75, 0.0625]], dtype=np.float32)
+    v = np.array([-3, -2.5, -2, -1.25, -1, -0.5, 0, 0.25, 0.5, 0.75, 1, 1.5, 2, 2.75, 3, 3.25, 4, 4.5])
+    g = np.stack(np.meshgrid(v, v, v, indexing='ij'), -1).reshape(-1, 3)
+    pts_batch = np.arange(g.shape[0]) % 2
+    p64 = min_pts[pts_batch].astype(np.float64) + g * res
+    pts = p64.astype(np.float32)
+    assert np.array_equal(pts.astype(np.float64), p64)                           # the queries are exact fp32 numbers
+    lv = _Interp(coords, feats, ts, min_pts, res, cuda)
+    rows, w, qc = lv.corners(pts, pts_batch, 1)
+    assert np.array_equal(qc.astype(np.float64), g * ts)                         # ... and so is the whole chain
+    integral = (g == np.floor(g)).sum(axis=1)
+    assert all((integral == k).sum() > 100 for k in (0, 1, 2, 3))                # interior, face, edge and lattice points
+    present = (rows >= 0).sum(axis=1)
+    assert set(present.tolist()) == set(range(9))                                # cells with 0 .. 8 corners present
+    assert (rows[(g < 0).any(axis=1)] >= 0).any()                                # rows below the minimum are found
+    val, s = lv.ref(pts, pts_batch, 1)
+    ref32 = val.astype(np.float32)
+    assert np.array_equal(ref32.astype(np.float64), val) and (s > 0).any(axis=1).sum() > 1000
+    out = lv.run(pts, pts_batch, 1)
+    assert np.array_equal(out, ref32.view(np.int32))
+    assert np.array_equal(lv.run(pts, pts_batch, 1), out)
+
+
+@pytest.mark.parametrize('ts', [1, 2, 4])
+def test_interp_generic_queries_within_nine_u_s(ts, cuda):
+    """Random queries, random features, res = 0.04, another min_pts per batch: every element within 9 u S of the float64 sum over
+    the checker's corners.  A kernel that picks another corner, or weights one an ulp off, has no tolerance to hide in."""
+    rng = np.random.default_rng(210 + ts)
+    res = 0.04
+    coords = _lattice_map(rng, 8, -2, ts, 0.55)
+    feats = rng.standard_normal((coords.shape[0], 32)).astype(np.float32)
+    min_pts = rng.uniform(-3, 3, (2, 3)).astype(np.float32)
+    n_pts, n_hyp = 700, 3
+    pts_batch = rng.integers(0, 2, n_pts)
+    pts = (min_pts[pts_batch][:, None, :] + rng.uniform(-3.5, 7.5, (n_pts, n_hyp, 3)) * res).astype(np.float32)
+    lv = _Interp(coords, feats, ts, min_pts, res, cuda)
+    rows, _, _ = lv.corners(pts, pts_batch, n_hyp)
+    assert set((rows >= 0).sum(axis=1).tolist()) == set(range(9))                # partly absent cells are present
+    val, s = lv.ref(pts, pts_batch, n_hyp)
+    out = lv.run(pts, pts_batch, n_hyp)
+    _check_bound(out, val, s, 'generic ts=%d' % ts)
+    assert np.array_equal(lv.run(pts, pts_batch, n_hyp), out)
+
+
+@pytest.mark.parametrize('exact', [False, True])
+@pytest.mark.parametrize('ts', [1, 2])
+def test_interp_away_from_the_occupied_voxels(ts, exact, cuda):
+    """Queries below min_pts by 1, 8, 9 and 100 voxels, beyond 60 000 voxels, 10^6 m away, and in cells with 1 .. 7 corners
+    present: the checker's value, which is exact zero where no corner is present.  ``exact``: res = 2^-5 and min_pts multiples of
+    it, so that the queries ARE the intended lattice positions and the rows at -8 and 60 000 are provably reached."""
+    rng = np.random.default_rng(220 + ts + 10 * exact)
+    res = 0.03125 if exact else 0.04
+    far = 60000 // ts * ts
+    extra = [(0, -8, -8, -8), (0, -8, 0, 0), (1, 0, -8, 0), (0, far, 0, 0), (0, far + ts, 0, 0), (0, far - ts, 0, 0),
+             (1, 0, 0, far), (1, 0, 0, far + ts), (0, so.COORD_MAX // ts * ts, 0, 0)]
+    coords = _lattice_map(rng, 6, 0, ts, 0.5, extra=extra)
+    feats = rng.standard_normal((coords.shape[0], 8)).astype(np.float32) + 3.0
+    min_pts = np.array([[-1.5, 0.25, 2.0], [0.5, -2.0, 1.0]], dtype=np.float32) if exact else rng.uniform(-2, 2, (2, 3)).astype(np.float32)
+    L = far / ts                                                                 # lattice units (voxels of this level)
+    m8 = -8 / ts                                                                 # lattice position of coordinate -8
+    groups = [                                                                   # (name, batch, queries in lattice units)
+        ('origin', 0, [(m8, m8, m8)]),
+        ('below_1', 0, [(-1, .25, .5), (-1, 0, 0)]),
+        ('at_minus_8', 0, [(m8 + .25, m8 + .5, m8), (m8, 0, 0), (m8 - .5, 0, 0), (-8, .5, .5), (-8.25, 1, 1)]),
+        ('below_9', 0, [(-9, .5, .5), (-9, 0, 0), (-9.5, -9.5, -9.5)]),
+        ('below_100', 0, [(-100, 1, 1), (1, -100, 1), (1, 1, -100)]),
+        ('around_60000', 0, [(L - .5, 0, 0), (L, 0, 0), (L + .5, 0, 0), (L + 1, 0, 0), (L + 10, 5, 5), (L - 1, .5, .5),
+                             (65519 // ts, 0, 0)]),
+        ('beyond_70000', 0, [(70000, 1, 1)]),
+        ('far_1e6_m', 0, [(1e6 / res, 0, 0), (0, 1e6 / res, 0), (1e6 / res, 1e6 / res, 1e6 / res)]),
+        ('batch_1', 1, [(0, 0, L), (0, 0, L + .5), (.5, .5, L - .5), (0, m8, 0), (.5, m8 - .25, 0), (0, 0, L + 1)])]
+    vr = rng.uniform(-1, 6, (800, 3))
+    if exact:
+        vr = np.round(vr * 8) / 8
+    g = np.concatenate([np.array(q, dtype=np.float64) for _, _, q in groups] + [vr])
+    name = np.array([n for n, _, q in groups for _ in q] + ['random'] * 800)
+    pts_batch = np.concatenate([np.full(len(q), b) for _, b, q in groups] + [rng.integers(0, 2, 800)])
+    pts = (min_pts[pts_batch].astype(np.float64) + g * res).astype(np.float32)
+    lv = _Interp(coords, feats, ts, min_pts, res, cuda)
+    rows, w, qc = lv.corners(pts, pts_batch, 1)
+    present = (rows >= 0).sum(axis=1)
+    assert set(range(1, 8)) <= set(present[name == 'random'].tolist())          # cells with 1 .. 7 corners present
+    for far_group in ('below_100', 'beyond_70000', 'far_1e6_m'):
+        assert (name == far_group).any() and (present[name == far_group] == 0).all()
+    table = {tuple(r): i for i, r in enumerate(coords.tolist())}
+    beyond = [table[(0, far + ts, 0, 0)], table[(1, 0, 0, far + ts)], table[(0, so.COORD_MAX // ts * ts, 0, 0)]]
+    assert not np.isin(rows, beyond).any()                                       # in the table, past the guard: never a corner
+    if exact:
+        assert np.array_equal(qc.astype(np.float64), g * ts)
+        found = set(rows[rows >= 0].tolist())
+        assert {table[(0, -8, -8, -8)], table[(0, -8, 0, 0)], table[(1, 0, -8, 0)], table[(0, far, 0, 0)], table[(1, 0, 0, far)]} <= found
+        o = int(np.nonzero(name == 'origin')[0][0])
+        assert rows[o, 0] == table[(0, -8, -8, -8)] and w[o, 0] == 1.0           # on the lattice point (-8, -8, -8) itself
+    val, s = lv.ref(pts, pts_batch, 1)
+    out = lv.run(pts, pts_batch, 1)
+    _check_bound(out, val, s, 'away ts=%d exact=%d' % (ts, exact))
+    zero = (s == 0).all(axis=1)
+    assert zero.sum() >= 10 and (out[zero] == 0).all()                           # +0.0, bit for bit
+
+
+@pytest.mark.parametrize('C', [4, 8, 16, 32, 64, 128, 256, 1024])
+def test_interp_channel_counts_and_wide_row_layout(C, cuda):
+    """Every supported channel count x (n_pts, n_hyp) with n_pts n_hyp in {1, 31, 32, 33, 257}, written at column col0 > 0 of rows
+    of ld_out > C floats: the values within 9 u S, the columns outside [col0, col0 + C) keep their bits, two launches agree."""
+    rng = np.random.default_rng(230 + C)
+    ts, res = 2, 0.04
+    coords = _lattice_map(rng, 5, -1, ts, 0.5)
+    feats = rng.standard_normal((coords.shape[0], C)).astype(np.float32)
+    min_pts = rng.uniform(-1, 1, (2, 3)).astype(np.float32)
+    lv = _Interp(coords, feats, ts, min_pts, res, cuda)
+    col0, ld = 5, C + 11
+    worst = 0.0
+    for n_pts, n_hyp in ((1, 1), (31, 1), (4, 8), (11, 3), (257, 1), (33, 8)):
+        pts_batch = np.arange(n_pts) % 2 if n_pts > 1 else np.array([1])
+        pts = (min_pts[pts_batch][:, None, :] + rng.uniform(-2.5, 5.5, (n_pts, n_hyp, 3)) * res).astype(np.float32)
+        if n_pts == 1:                                                           # the single query sits inside an occupied cell
+            row = coords[coords[:, 0] == 1][0, 1:]
+            pts = (min_pts[1] + (row / ts + 0.3) * res).astype(np.float32).reshape(1, 1, 3)
+        val, s = lv.ref(pts, pts_batch, n_hyp)
+        assert (s > 0).any()
+        out = lv.run(pts, pts_batch, n_hyp, ld_out=ld, col0=col0)
+        assert out.shape == (n_pts * n_hyp, ld)
+        assert (out[:, :col0] == SENTINEL).all() and (out[:, col0 + C:] == SENTINEL).all()
+        worst = max(worst, _check_bound(np.ascontiguousarray(out[:, col0:col0 + C]), val, s, 'C=%d n_pts=%d n_hyp=%d' % (C, n_pts, n_hyp)))
+        assert np.array_equal(lv.run(pts, pts_batch, n_hyp, ld_out=ld, col0=col0), out)
+    assert worst > 0                                                             # fp32 sums of random data do round somewhere
+
+
+def test_interp_error_codes_leave_the_output_untouched(cuda):
+    rng = np.random.default_rng(240)
+    coords = _lattice_map(rng, 4, 0, 1, 0.7)
+    feats = rng.standard_normal((coords.shape[0], 16)).astype(np.float32)
+    min_pts = np.zeros((2, 3), dtype=np.float32)
+    lv = _Interp(coords, feats, 1, min_pts, 0.04, cuda)
+    pts_batch = np.arange(50) % 2
+    pts = (rng.uniform(0, 3, (50, 2, 3)) * 0.04).astype(np.float32)
+    for C in (6, 12):
+        assert (lv.run(pts, pts_batch, 2, C=C, ld_out=16, expect=UNSUPPORTED) == SENTINEL).all()
+    assert (lv.run(pts, pts_batch, 2, ws_short=1, expect=WS_SMALL) == SENTINEL).all()
+    assert (lv.run(pts, pts_batch, 2, n_pts=0, expect=OK) == SENTINEL).all()      # nothing to do: OK, nothing written
+    out = lv.run(pts, pts_batch, 2)                                              # and the same call, complete, does work
+    val, s = lv.ref(pts, pts_batch, 2)
+    _check_bound(out, val, s, 'after the rejected calls')
+
+
+# ---- fused decoder against the unfused chain at the same edges ---------------------------------------------------------------------
+
+def _scene_cloud():
+    """A synthetic two-batch cloud of a few hundred voxels.  The voxel size is 2^-4 and the origins are multiples of it, so that
+    voxel positions -- the lattice planes of every level -- are exact fp32 numbers."""
+    rng = np.random.default_rng(300)
+    res = 0.0625
+    origin = np.array([[-1.0, 0.5, 2.0], [3.0, -2.0, 0.25]])
+    idx, batch = [], []
+    for b in (0, 1):
+        blk = _block(9, 0, batches=[b])[:, 1:]
+        blk = blk[(blk[:, 2] < 7) & (rng.random(blk.shape[0]) < 0.4)]
+        idx.append(blk)
+        batch.append(np.full(blk.shape[0], b))
+    idx, batch = np.concatenate(idx), np.concatenate(batch)
+    assert 300 < idx.shape[0] < 600
+    pts = origin[batch] + idx * res
+    feat = rng.standard_normal((idx.shape[0], 64)).astype(np.float32)
+    return idx, batch, pts, feat, origin, res
+
+
+@pytest.fixture(scope='module')
+def scene(cuda):
+    """The three-level structure SparseUNet builds on that cloud."""
+    syn, sm = v3d('synthetic'), v3d('scenemodeling')
+    idx, batch, pts, feat, origin, res = _scene_cloud()
+    net = sm.SparseUNet().eval()
+    net.load_state_dict(syn.sparse_unet_weights(seed=4))
+    with torch.no_grad():
+        xs = net.to(cuda)(_to(feat, cuda, torch.float32), _to(pts, cuda, torch.float32), _to(idx, cuda, torch.int32),
+                          _to(batch, cuda, torch.int64), res)
+    assert [int(x['stride']) for x in xs] == [4, 2, 1]
+    levels = [dict(coords=x['sparse'].coords.cpu().numpy().astype(np.int64), feats=x['feats'].cpu().numpy(), ts=int(x['stride']),
+                   res=float(x['res']), min_pts=x['_min_pts'].cpu().numpy(), pts=x['pts'].cpu().numpy(),
+                   batch=x['batch'].cpu().numpy().astype(np.int64)) for x in xs]
+    return xs, levels, origin, res
+
+
+def _decoder_queries(levels, origin, res, n_hyp, seed):
+    """~300 points x n_hyp.  Hypothesis 0 of every point is its base position; the others step away from it."""
+    rng = np.random.default_rng(seed)
+    base, batch, kind = [], [], []
+    for l, lv in enumerate(levels):                              # on the lattice of level l: voxel positions of that level
+        pick = rng.choice(lv['pts'].shape[0], 25, replace=False)
+        base.append(lv['pts'][pick].astype(np.float64)); batch.append(lv['batch'][pick]); kind += ['lattice%d' % l] * 25
+        pick = rng.choice(lv['pts'].shape[0], 20, replace=False)  # on ONE lattice plane: the other two axes anywhere
+        p = lv['pts'][pick].astype(np.float64)
+        ax = rng.integers(0, 3, 20)
+        rnd = origin[lv['batch'][pick]] + rng.uniform(-0.5, 9.0, (20, 3)) * res
+        keep = np.arange(3)[None, :] == ax[:, None]
+        base.append(np.where(keep, p, rnd)); batch.append(lv['batch'][pick]); kind += ['plane%d' % l] * 20
+    for l, lv in enumerate(levels):                              # below the level minimum
+        b = rng.integers(0, 2, 10)
+        base.append(lv['min_pts'][b].astype(np.float64) - rng.choice([0.5, 1, 2.5, 9], (10, 1)) * lv['res'] * (rng.random((10, 3)) < 0.7))
+        batch.append(b); kind += ['below'] * 10
+    b = rng.integers(0, 2, 110)                                   # anywhere in and around the occupied box
+    base.append(origin[b] + rng.uniform(-1.5, 10.0, (110, 3)) * res); batch.append(b); kind += ['random'] * 110
+    b = rng.integers(0, 2, 12)                                    # far outside
+    base.append(origin[b] + rng.choice([50.0, -50.0, 3000.0, 1e6], (12, 1)) * (rng.random((12, 3)) < 0.6).clip(0, 1) + 40.0)
+    batch.append(b); kind += ['far'] * 12
+    base, batch, kind = np.concatenate(base), np.concatenate(batch), np.array(kind)
+    step = rng.standard_normal((base.shape[0], 1, 3)) * 0.03
+    pts = base[:, None, :] + step * np.arange(n_hyp)[None, :, None]
+    return pts.astype(np.float32), batch.astype(np.int64), kind
+
+
+def _decoder_case(levels, origin, res, n_hyp):
+    """The query set of one hypothesis count, with the conditions that make it worth running asserted on the checker."""
+    pts, pts_batch, kind = _decoder_queries(levels, origin, res, n_hyp, seed=310 + n_hyp)
+    n_pts = pts.shape[0]
+    assert 280 <= n_pts <= 330 and set(pts_batch.tolist()) == {0, 1}
+    for l, lv in enumerate(levels):
+        rows, w, qc = so.corner_table(lv['coords'], lv['ts'], pts, pts_batch, n_hyp, lv['min_pts'], lv['res'])
+        q0 = (qc.reshape(n_pts, n_hyp, 3)[:, 0] / np.float32(lv['ts'])).astype(np.float64)
+        on = q0 == np.floor(q0)
+        assert on[kind == 'lattice%d' % l].all() and (on[kind == 'plane%d' % l].sum(axis=1) >= 1).all()
+        present = (rows >= 0).sum(axis=1)
+        # partly absent cells at every level (the coarsest is nearly full: there they lie on the border), of several kinds at the finest
+        assert ((present > 0) & (present < 8)).sum() >= 20 and (present == 0).sum() >= 12 * n_hyp
+        assert l < 2 or len(set(range(1, 8)) & set(present.tolist())) >= 4
+        below = (qc < 0).any(axis=1)
+        assert below.sum() >= 10 and (rows[below] >= 0).any()
+    return pts, pts_batch
+
+
+@pytest.mark.parametrize('n_hyp', [1, 5, 8])
+def test_fused_decoder_and_unfused_chain_at_the_edges(n_hyp, scene, cuda):
+    """Queries on lattice planes of each level (qc / ts integral, asserted with the checker), below the level minimum, in cells with
+    partly absent corners and far outside: HypothesisDecoder.features per element against the checker, level by level, within
+    9 u S; decode_fused against decode(features) at the tolerances of test_fused_decoder_matches_unfused_chain_and_golden."""
+    syn, rf = v3d('synthetic'), v3d('refinement')
+    xs, levels, origin, res = scene
+    pts, pts_batch = _decoder_case(levels, origin, res, n_hyp)
+    n_pts = pts.shape[0]
+    dec = rf.HypothesisDecoder(320, 128, 3, 1).eval()
+    dec.load_state_dict(syn.decoder_weights(in_dim=320, h_dim=128, seed=6, sharpen=100.0), strict=False)
+    dec = dec.to(cuda)
+    p, pb = _to(pts, cuda, torch.float32), _to(pts_batch, cuda, torch.int64)
+    vals = torch.linspace(-0.1, 0.1, n_hyp).to(cuda) if n_hyp > 1 else torch.tensor([0.05], device=cuda)
+    with torch.no_grad():
+        feats = dec.features(xs, p, None, pb)
+        assert dec.can_fuse(xs, p, None)
+        p_f, e_f = dec.decode_fused(xs, p, None, pb, vals)
+        p_u, e_u = dec.decode(feats, vals)
+    torch.cuda.synchronize()
+    f = feats.cpu().numpy().reshape(n_pts * n_hyp, 320)
+    col = 0
+    for l in (2, 1, 0):                                           # feature rows hold the finest level first
+        lv = levels[l]
+        C = lv['feats'].shape[1]
+        val, s = so.interp(lv['coords'], lv['feats'], lv['ts'], pts, pts_batch, n_hyp, lv['min_pts'], lv['res'])
+        _check_bound(np.ascontiguousarray(f[:, col:col + C]).view(np.int32), val, s, 'features level stride %d, n_hyp=%d' % (lv['ts'], n_hyp))
+        col += C
+    assert col == 320
+    p_f, p_u, e_f, e_u = (t.cpu().numpy() for t in (p_f, p_u, e_f, e_u))
+    print('n_hyp=%d: max |p_fused - p_unfused| = %.3e, max |e_fused - e_unfused| = %.3e, largest probability %.3f, smallest row maximum %.3f'
+          % (n_hyp, np.abs(p_f - p_u).max(), np.abs(e_f - e_u).max(), p_u.max(), p_u.max(axis=1).min()))
+    # One hypothesis: the softmax is identically 1 and the expectation vals[0] (the library exposes no logits), so for that
+    # parameter only the per-level feature check above does any work -- and the comparison below that a one-column tile runs at all.
+    # Otherwise: a peaked softmax, as in test_fused_decoder_matches_unfused_chain_and_golden.
+    if n_hyp == 1:
+        assert (p_u == 1).all() and np.abs(e_u - vals[0].item()).max() <= 1e-7
+    else:
+        assert float(p_u.max()) > 0.5
+    np.testing.assert_allclose(p_f, p_u, rtol=0, atol=1e-4)
+    np.testing.assert_allclose(e_f, e_u, rtol=0, atol=2e-5)

@@ -150,6 +150,10 @@ SIGNATURES = {
                                      c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     'v3d_mesh_render_depth_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_double, c_double,
                                           c_double, c_void_p, c_void_p, c_void_p]),
+    'v3d_tsdf_resample_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_float_p, c_float_p, c_int, c_int,
+                                      c_int, c_int, c_float_p, c_void_p, c_void_p, c_void_p]),
+    'v3d_volume_resample_nearest': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_float_p, c_float_p, c_int, c_int,
+                                            c_int, c_int, c_float_p, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -76,6 +76,9 @@ def build(force=False, verbose=False, strict=False):
             isa_check.check_no_scratch(os.path.join(objdir, 'fusion.o'), 'fuse_depths_kernel', strict=strict)
             # TSDF integration: the five running values of a voxel stay in registers across the view loop
             isa_check.check_no_scratch(os.path.join(objdir, 'tsdf.o'), 'tsdf_integrate_kernel', strict=strict)
+            # TSDF resampling: the coordinate, the eight tap indices and weights of an output voxel stay in registers
+            isa_check.check_no_scratch(os.path.join(objdir, 'tsdf_resample.o'), 'tsdf_resample_kernel', strict=strict)
+            isa_check.check_no_scratch(os.path.join(objdir, 'tsdf_resample.o'), 'volume_resample_nearest_kernel', strict=strict)
             # nearest neighbour: the per-query search state of nn_query_kernel stays in registers
             isa_check.check_no_scratch(os.path.join(objdir, 'cloudmetrics.o'), 'nn_query_kernel', strict=strict)
             # mesh extraction: the status bytes of a cell, its table row and the vertex state stay in registers

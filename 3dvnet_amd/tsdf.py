@@ -11,6 +11,10 @@ volume with weights and colours (``mv3d/eval/tsdf_atlas.py``: ``TSDFFusion`` :34
   * ``fuse_preds_tsdf``      from a ``preds.npz`` record (path or mapping) to the ``TSDF``;
   * ``TSDF.get_mesh``        the volume -> a ``mesh.TriangleMesh`` on the device (``csrc/mesh.hip``: marching cubes with the
                              project's own case table and the reference's rules around it, tsdf_atlas.py:161-253);
+  * ``TSDF.transform``       the volume resampled onto another grid and / or through a 3 x 4 transform (``csrc/tsdf_resample.hip``
+                             behind ``v3d_tsdf_resample_f32`` / ``v3d_volume_resample_nearest``; tsdf_atlas.py:255-338);
+  * ``eval_tsdf``            the volume metric (``mv3d/baselines/atlas/evaluation.py:24-96``): the prediction aligned to the
+                             target's grid by ``transform``, then ``l1`` / ``l1_ns``;
   * ``tsdf_mesh_metrics``    the rest of the ``run_tsdf`` branch (:383-397): mesh -> vertices -> down-sample -> 3D metrics;
   * ``trim_mesh``            a mesh cut down to what given cameras saw (:71-150): rendered into every view
                              (``meshtodepth``), the renderings integrated into a fresh volume, that volume meshed;
@@ -19,8 +23,9 @@ volume with weights and colours (``mv3d/eval/tsdf_atlas.py``: ``TSDFFusion`` :34
 ``gt_mesh`` / ``mask_mesh`` arguments are the reference's ``MASK_USING_GT_MESH`` switch: depths are zeroed where a rendering of
 that mesh sees nothing (``meshtodepth.mask_with_mesh``).
 
-There is no CPU fallback: without the library or a HIP device every integrating, meshing or rendering entry raises
-``V3DLibraryError``.  ``TSDF.transform`` and the label volume are not provided.
+There is no CPU fallback: without the library or a HIP device every integrating, meshing, rendering or resampling entry raises
+``V3DLibraryError``.  The label volume is not provided; ``transform`` carries integer and bool volumes that
+arrive through the constructor or ``load``.
 """
 import ctypes
 
@@ -94,8 +99,8 @@ class TSDF:
 
     ``save`` writes the reference's npz keys: ``origin``, ``voxel_size``, ``tsdf`` and one key per attribute volume /
     attribute.  ``load`` reads them back the way the reference does, including its placement of ``weight`` (and
-    ``tsdf_point_cloud``) under ``attributes`` rather than ``attribute_vols``.  ``get_mesh`` runs on the device;
-    ``transform`` is not provided."""
+    ``tsdf_point_cloud``) under ``attributes`` rather than ``attribute_vols``.  ``get_mesh`` and ``transform`` run on the
+    device."""
 
     def __init__(self, voxel_size, origin, tsdf_vol, attribute_vols=None, attributes=None):
         self.voxel_size = voxel_size
@@ -151,6 +156,147 @@ class TSDF:
         color = self.attribute_vols.get('color') if attribute == 'color' else None
         verts, colors, tris = _mesh.extract(self.tsdf_vol, color, self.voxel_size, self.origin, _mesh.MODE_MESH)
         return _mesh.TriangleMesh(verts, tris, colors)
+
+    def transform(self, transform=None, voxel_dim=None, origin=None, align_corners=False):
+        """The reference's ``transform`` (tsdf_atlas.py:255-338) -> a new ``TSDF`` on the same device, resampled onto the
+        grid ``voxel_dim`` (default: this volume's) at ``origin`` (default: this volume's), with the same voxel size.
+        ``transform`` [3, 4] or [4, 4] (host or device; read to the host once as 12 floats; None = identity) maps the world
+        coordinates of the new grid to those of this volume.  ``align_corners`` is ``grid_sample``'s, default False as in
+        the reference (``eval_tsdf`` passes True, with which an integer shift does not interpolate).
+
+        tsdf: the nearest value; where that has magnitude < 1 the trilinear one; 1 where the voxel lies outside this
+        volume (some normalised coordinate of magnitude >= 1 -- which includes this volume's border layer).  fp32 attribute
+        volumes [nx, ny, nz] / [C, nx, ny, nz]: trilinear with zero padding.  Every other dtype (integer labels, bool masks,
+        float64): nearest with zero padding, the element copied in its own type -- equal to the reference's route through
+        fp32 for |value| < 2^24, a stated deviation beyond.  Outside, ``'semseg'`` becomes -1 and ``'mask_outside'`` True.
+        ``attributes`` is passed through as the same dict.  The result's ``origin`` is [1, 3] fp32; shapes are
+        [nx, ny, nz] / [C, nx, ny, nz] without the reference's ``.squeeze()`` (a difference only when a size is 1).
+        One launch for the tsdf together with the first fp32 attribute volume, one per other attribute volume
+        (csrc/tsdf_resample.hip; the arithmetic is pinned in include/v3d.h).  No CPU fallback."""
+        lib = _lib.load()
+        dev = self.tsdf_vol.device
+        if self.tsdf_vol.dim() != 3 or self.tsdf_vol.dtype != torch.float32:
+            raise ValueError('TSDF.transform: tsdf_vol must be [nx, ny, nz] fp32, got %s %s'
+                             % (tuple(self.tsdf_vol.shape), self.tsdf_vol.dtype))
+        src_dim = tuple(int(v) for v in self.tsdf_vol.shape)
+        if min(src_dim) < 2:
+            raise ValueError('TSDF.transform: the volume is %s; every size must be at least 2 (the coordinates are normalised '
+                             'by size - 1)' % (src_dim,))
+        if transform is None:
+            mat = torch.eye(4)[:3]
+        else:
+            mat = torch.as_tensor(transform).detach().to('cpu', torch.float32)
+            if tuple(mat.shape) not in ((3, 4), (4, 4)):
+                raise ValueError('TSDF.transform: transform must be [3, 4] or [4, 4], got %s' % (tuple(mat.shape),))
+            mat = mat[:3]
+        if not bool(torch.isfinite(mat).all()):
+            raise ValueError('TSDF.transform: transform is not finite')
+        dim = src_dim if voxel_dim is None else tuple(int(v) for v in voxel_dim)
+        if len(dim) != 3 or min(dim) < 1 or dim[0] * dim[1] * dim[2] >= 2 ** 31:
+            raise ValueError('TSDF.transform: voxel_dim %r (three positive sizes, fewer than 2^31 voxels)' % (voxel_dim,))
+        src_origin = torch.as_tensor(self.origin).detach().to('cpu', torch.float32).reshape(-1)
+        new_origin = src_origin if origin is None else torch.as_tensor(origin).detach().to('cpu', torch.float32).reshape(-1)
+        if src_origin.numel() != 3 or new_origin.numel() != 3:
+            raise ValueError('TSDF.transform: an origin has three components')
+        if not bool(torch.isfinite(src_origin).all() and torch.isfinite(new_origin).all()):
+            raise ValueError('TSDF.transform: an origin is not finite')
+        vs = float(self.voxel_size)
+        if not (np.isfinite(vs) and vs > 0):
+            raise ValueError('TSDF.transform: voxel_size=%r (positive and finite)' % (self.voxel_size,))
+        vols = {}
+        for key, value in self.attribute_vols.items():
+            if value.dim() not in (3, 4) or tuple(value.shape[-3:]) != src_dim:
+                raise ValueError('TSDF.transform: attribute volume %r is %s; [nx, ny, nz] or [C, nx, ny, nz] on the grid %s expected'
+                                 % (key, tuple(value.shape), src_dim))
+            if value.element_size() not in (1, 2, 4, 8) or value.is_complex():
+                raise ValueError('TSDF.transform: attribute volume %r has dtype %s' % (key, value.dtype))
+        if not torch.cuda.is_available() or not self.tsdf_vol.is_cuda:
+            raise _lib.V3DLibraryError('TSDF.transform: the volume must live on a HIP device (no CPU fallback)')
+        for key, value in self.attribute_vols.items():
+            vols[key] = value.to(dev).contiguous()
+        grid = (src_dim[0], src_dim[1], src_dim[2], vs, (ctypes.c_float * 3)(*src_origin.tolist()),
+                (ctypes.c_float * 12)(*mat.reshape(-1).tolist()), 1 if align_corners else 0, dim[0], dim[1], dim[2],
+                (ctypes.c_float * 3)(*new_origin.tolist()))
+        tsdf_src = self.tsdf_vol.contiguous()
+        tsdf_dst = torch.empty(dim, dtype=torch.float32, device=dev)
+        out = {}
+        fused = next((k for k, v in vols.items() if v.dtype == torch.float32), None)
+        with torch.cuda.device(dev):
+            stream = _lib.stream_ptr(dev)
+            for key, value in vols.items():
+                channels = 1 if value.dim() == 3 else int(value.shape[0])
+                dst = torch.empty(tuple(value.shape[:-3]) + dim, dtype=value.dtype, device=dev)
+                out[key] = dst
+                if channels == 0:
+                    continue
+                if value.dtype == torch.float32:
+                    with_tsdf = key == fused
+                    _lib.check(lib.v3d_tsdf_resample_f32(_lib.ptr(tsdf_src) if with_tsdf else None, _lib.ptr(value), channels, *grid,
+                                                         _lib.ptr(tsdf_dst) if with_tsdf else None, _lib.ptr(dst), stream),
+                               'v3d_tsdf_resample_f32')
+                else:
+                    fill = {'semseg': -1, 'mask_outside': True}.get(key)
+                    fill_bytes = None if fill is None else torch.tensor([fill]).to(value.dtype).numpy().tobytes()
+                    _lib.check(lib.v3d_volume_resample_nearest(_lib.ptr(value), value.element_size(), channels, *grid,
+                                                               0 if fill is None else 1, fill_bytes, _lib.ptr(dst), stream),
+                               'v3d_volume_resample_nearest')
+            if fused is None or out[fused].numel() == 0:
+                _lib.check(lib.v3d_tsdf_resample_f32(_lib.ptr(tsdf_src), None, 0, *grid, _lib.ptr(tsdf_dst), None, stream),
+                           'v3d_tsdf_resample_f32')
+        return TSDF(self.voxel_size, new_origin.view(1, 3).to(dev), tsdf_dst, out, self.attributes)
+
+
+def _masked_l1(pred, trgt, non_surface_only):
+    """Mean |pred - trgt| over the target's observed voxels (``weight != 0``; with ``non_surface_only`` also ``trgt < 1``), as a
+    float64 sum on the prediction's device; NaN for an empty mask, as ``F.l1_loss`` gives."""
+    if float(pred.voxel_size) != float(trgt.voxel_size):
+        raise ValueError('l1: voxel sizes %r and %r differ' % (pred.voxel_size, trgt.voxel_size))
+    if tuple(pred.tsdf_vol.shape) != tuple(trgt.tsdf_vol.shape):
+        raise ValueError('l1: volumes of %s and %s voxels are not aligned (eval_tsdf aligns them)'
+                         % (tuple(pred.tsdf_vol.shape), tuple(trgt.tsdf_vol.shape)))
+    dev = pred.tsdf_vol.device
+    if not torch.equal(torch.as_tensor(pred.origin).reshape(-1).float().cpu(), torch.as_tensor(trgt.origin).reshape(-1).float().cpu()):
+        raise ValueError('l1: the origins differ (eval_tsdf aligns the volumes)')
+    weight = trgt.attributes.get('weight', trgt.attribute_vols.get('weight'))
+    if weight is None:
+        raise ValueError("l1: the target carries no 'weight' (which voxels were observed)")
+    t = trgt.tsdf_vol.to(dev)
+    mask = weight.to(dev).reshape(t.shape) != 0
+    if non_surface_only:
+        mask = mask & (t < 1.)
+    diff = (pred.tsdf_vol.double() - t.double()).abs()
+    return (diff[mask].sum() / mask.sum()).item()
+
+
+def l1(pred, trgt):
+    """The reference's ``l1`` (mv3d/baselines/atlas/evaluation.py:61-77) of two aligned ``TSDF``: the mean absolute difference
+    over the voxels the target observed (``trgt.attributes['weight'] != 0``, as ``TSDF.load`` places it; a ``'weight'``
+    attribute volume serves too)."""
+    return _masked_l1(pred, trgt, False)
+
+
+def l1_ns(pred, trgt):
+    """The reference's ``l1_ns`` (:80-96): ``l1`` restricted further to ``trgt < 1``."""
+    return _masked_l1(pred, trgt, True)
+
+
+def eval_tsdf(pred, trgt, device=None):
+    """The reference's volume metric (mv3d/baselines/atlas/evaluation.py:24-51) -> ``{'l1': ..., 'l1_ns': ...}``.  ``pred`` and
+    ``trgt`` are ``TSDF`` objects or npz paths (read with ``TSDF.load`` and moved to ``device``, default the first HIP device).
+    The prediction is brought onto the target's grid by ``transform(voxel_dim=..., origin=..., align_corners=True)``; the
+    shift between the two origins must be a whole number of voxels (``torch.allclose``'s rule), else ``ValueError``.  The two
+    means are stock torch ops with float64 sums: once per scene, not a hot path."""
+    def get(v):
+        if isinstance(v, TSDF):
+            return v
+        return TSDF.load(v).to(_fusion._device(device))
+    pred, trgt = get(pred), get(trgt)
+    shift = (torch.as_tensor(trgt.origin).float().cpu() - torch.as_tensor(pred.origin).float().cpu()) / trgt.voxel_size
+    if not torch.allclose(shift, shift.round()):
+        raise ValueError('eval_tsdf: the origins differ by %s voxels, not by a whole number' % (shift.reshape(-1).tolist(),))
+    pred = pred.transform(voxel_dim=list(trgt.tsdf_vol.shape), origin=torch.as_tensor(trgt.origin).detach().cpu(),
+                          align_corners=True)
+    return {'l1': l1(pred, trgt), 'l1_ns': l1_ns(pred, trgt)}
 
 
 class TSDFFusion:

@@ -637,6 +637,47 @@ int v3d_mesh_render_depth_f32(const float* verts, int n_vert, const int32_t* tri
                               int h, int w, double pixel_center, double znear, double zfar, float* depth, int32_t* status,
                               void* stream);
 
+/* Resampling of a TSDF volume onto another grid (csrc/tsdf_resample.hip): the semantics of mv3d/eval/tsdf_atlas.py TSDF.transform
+ * (:255-338) -- crop / pad to another voxel_dim and origin and / or apply a 3 x 4 transform; the first step of eval_tsdf
+ * (mv3d/baselines/atlas/evaluation.py:24-51).  ABI version: STILL 9 (additive, as the TSDF, mesh and render symbols are).
+ *   Volumes (DEVICE), z fastest: source [sx, sy, sz] at src_origin, output [nx, ny, nz] at dst_origin, both with voxel_size;
+ *   channel c of a [C, ...] volume starts at c * (number of voxels).  src_origin [3], dst_origin [3] and matrix [12] (3 x 4, row
+ *   major, maps OUTPUT world coordinates to SOURCE world coordinates) are HOST arrays read before the call returns; voxel_size is
+ *   taken as fp32.
+ *   Per output voxel (ix, iy, iz) and axis a with source size D_a, all fp32, every operation rounded on its own unless stated:
+ *     world_a = fl(fl(i_a * voxel_size) + dst_origin_a)                       (the function of v3d_tsdf_integrate_f32)
+ *     t_a     = row a of matrix . [world; 1], a k-ordered FMA chain whose homogeneous term is a rounded addition (dot4h_chain)
+ *     c_a     = fl(fl(t_a - src_origin_a) / voxel_size)                       (IEEE division)
+ *     g_a     = fl(fl(fl(2 c_a) / (D_a - 1)) - 1)                             grid_sample's normalised coordinate
+ *     u_a     = fl(fl(fl(g_a + 1) / 2) * (D_a - 1))                           align_corners != 0
+ *             = fl(fl(fl(fl(g_a + 1) * D_a) - 1) / 2)                         align_corners == 0 (the reference's default)
+ *     outside = some |g_a| >= 1 (a NaN is not outside).
+ *   Nearest: r_a = round-half-even(u_a); in bounds iff 0 <= r_a <= D_a - 1 on every axis, decided on the floats before any integer
+ *   conversion (a NaN or huge value is out of bounds); out of bounds gives 0 (zero padding).
+ *   Trilinear: f_a = floor(u_a), per axis w0_a = fl(fl(f_a + 1) - u_a) at f_a and w1_a = fl(u_a - f_a) at f_a + 1; tap weight =
+ *   fl(fl(w_z * w_y) * w_x); value = the sum over the taps inside the volume (same float test) of fl(src * weight), accumulated
+ *   from 0 in the order x outermost, z innermost, every addition rounded (no FMA): the order and roundings of torch's CPU
+ *   grid_sample.  Taps outside contribute nothing.
+ *   v3d_tsdf_resample_f32  ONE launch: the tsdf (tsdf_src -> tsdf_dst, both NULL: skipped) and `channels` fp32 channels (attr_src
+ *                         [C, sx, sy, sz] -> attr_dst [C, nx, ny, nz], both NULL with channels == 0) from one coordinate.  tsdf rule
+ *                         (:299-314): v = nearest; if |v| < 1, v = trilinear; if outside, v = 1.  Channels: trilinear, nothing else.
+ *                         The result of either part does not depend on whether the other is present.
+ *   v3d_volume_resample_nearest  `channels` channels of elements of elem_bytes = 1, 2, 4 or 8 bytes, copied in their own type
+ *                         (never through fp32): nearest, zero padding (all-zero bytes).  fill_outside = 1: where the voxel is outside,
+ *                         the elem_bytes bytes at fill_host (HOST) are written instead (the reference's semseg = -1 and mask_outside
+ *                         = True); 0: fill_host is not read.
+ * Asynchronous on `stream`; no workspace, no allocation, no atomics, no synchronisation; repeated calls give identical bits.
+ * Host-side errors, before any launch: V3D_ERR_BAD_ARG for a null required pointer (or one half of a src / dst pair), a voxel size
+ * that is not positive and finite, an origin or matrix entry that is not finite, an elem_bytes or fill_outside outside its set, a
+ * source that overlaps a destination; V3D_ERR_BAD_SHAPE for a source size < 2 (the normalisation divides by D - 1), an output
+ * size < 1, 2^31 or more voxels on either side, channels < 0 (< 1 for the nearest call). */
+int v3d_tsdf_resample_f32(const float* tsdf_src, const float* attr_src, int channels, int sx, int sy, int sz, double voxel_size,
+                          const float* src_origin_host, const float* matrix_host, int align_corners, int nx, int ny, int nz,
+                          const float* dst_origin_host, float* tsdf_dst, float* attr_dst, void* stream);
+int v3d_volume_resample_nearest(const void* src, int elem_bytes, int channels, int sx, int sy, int sz, double voxel_size,
+                                const float* src_origin_host, const float* matrix_host, int align_corners, int nx, int ny, int nz,
+                                const float* dst_origin_host, int fill_outside, const void* fill_host, void* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'lib3dvnet_hip.so')
 ABI_VERSION = 9
 PRECISION = {'split_bf16': 0, 'fp32': 1}      # V3D_PRECISION_* of include/v3d.h
+LAYOUT = {'reference': 0, 'split': 1, 'cl8': 2}   # V3D_LAYOUT_* (v3d_costreg_depth_prob)
 
 
 def precision_code(name):
@@ -154,6 +155,11 @@ SIGNATURES = {
                                       c_int, c_int, c_float_p, c_void_p, c_void_p, c_void_p]),
     'v3d_volume_resample_nearest': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_float_p, c_float_p, c_int, c_int,
                                             c_int, c_int, c_float_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'v3d_costreg_depth_prob': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_double, c_double] + [c_int] * 4 +
+                               [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'v3d_soft_argmin_f32': (c_int, [c_void_p, c_void_p, c_double, c_double] + [c_int] * 4 + [c_void_p, c_void_p, c_void_p]),
+    'v3d_confidence_logits_f32': (c_int, [c_void_p, c_void_p, c_double, c_double] + [c_int] * 4 + [c_void_p, c_void_p]),
+    'v3d_probability_map_f32': (c_int, [c_void_p, c_void_p, c_double, c_double] + [c_int] * 4 + [c_void_p, c_void_p]),
 }
 
 

@@ -2296,6 +2296,19 @@ int launch_soft_argmin(const float* xreg, const float* depth_vals, float* depth,
   return V3D_OK;
 }
 
+// The optional confidence output of the depth entry points (v3d_costreg_depth_prob): with `prob` set, the last launch is the
+// soft-argmin that also writes the confidence (confidence.hip: same depth bits); without it, soft_argmin_kernel as ever.
+struct ProbOut {
+  float* prob = nullptr;
+  double depth_start = 0., depth_interval = 0.;
+};
+
+int launch_depth_tail(const float* xreg, const float* depth_vals, float* depth, const ProbOut& po, int n, int D, int H, int W,
+                      hipStream_t s) {
+  if (!po.prob) return launch_soft_argmin(xreg, depth_vals, depth, n, D, H, W, s);
+  return v3d::launch_soft_argmin_prob(xreg, depth_vals, depth, po.prob, po.depth_start, po.depth_interval, n, D, H, W, s);
+}
+
 // conv9 + skip + prob: the tile kernel (split-bf16 or exact-fp32 operands)
 int launch_conv9_prob(bool f32, const v3d_costreg_weights* h, const float* u8, const float* c0, float* xreg, int n, int D, int H, int W,
                       hipStream_t s) {
@@ -2328,7 +2341,7 @@ int launch_conv9_prob(bool f32, const v3d_costreg_weights* h, const float* u8, c
 // The split-bf16 regulariser behind conv0, on the caller's stream: conv1 + conv2, conv3 .. conv8, conv9 + skip + prob,
 // soft-argmin.
 int run_split_tail(const v3d_costreg_weights* h, const WsPlan& ws, char* base, const float* depth_vals, int n, int D, int H, int W,
-                   float* depth, float* xreg, hipStream_t s) {
+                   float* depth, float* xreg, const ProbOut& po, hipStream_t s) {
   const size_t V1 = (size_t)D * H * W / 8;
   auto F = [&](size_t o) { return (float*)(base + o); };
   // conv1..conv6 hand their activations on in the split layout; the transposed convolutions read their skips (conv2, conv4)
@@ -2369,7 +2382,7 @@ int run_split_tail(const v3d_costreg_weights* h, const WsPlan& ws, char* base, c
   if ((rc = launch_deconvg<DG<32, 16, 14, kOutSplit, true>>("costreg_conv8", F(ws.u7), h->dev + h->dgbf_ofs[1], B_(8), c2s, nullptr,
                                                             F(ws.u8), n, D / 4, H / 4, W / 4, s)) != V3D_OK || stop_after < 9) return rc;
   if ((rc = launch_conv9_prob(false, h, F(ws.u8), F(ws.c0), xreg, n, D, H, W, s)) != V3D_OK || stop_after < 10) return rc;
-  return launch_soft_argmin(xreg, depth_vals, depth, n, D, H, W, s);
+  return launch_depth_tail(xreg, depth_vals, depth, po, n, D, H, W, s);
 }
 }  // namespace
 
@@ -2377,7 +2390,7 @@ int run_split_tail(const v3d_costreg_weights* h, const WsPlan& ws, char* base, c
 static int costreg_depth_impl(int in_layout, const v3d_costreg_weights* h, const float* var,
                               const float* depth_vals, int n, int D, int H, int W,
                               float* depth, float* reg, int precision, void* workspace,
-                              size_t workspace_bytes, void* stream) {
+                              size_t workspace_bytes, void* stream, const ProbOut& po = ProbOut()) {
   V3D_REQUIRE(precision == V3D_PRECISION_SPLIT_BF16 || precision == V3D_PRECISION_FP32, V3D_ERR_BAD_ARG,
               "v3d_costreg_depth_f32: unknown precision %d", precision);
   V3D_REQUIRE(h && var && depth_vals && depth && workspace, V3D_ERR_BAD_ARG,
@@ -2431,7 +2444,7 @@ static int costreg_depth_impl(int in_layout, const v3d_costreg_weights* h, const
       }
     }
     // conv1 .. conv9 + prob, soft-argmin
-    return run_split_tail(h, ws, base, depth_vals, n, D, H, W, depth, xreg, s);
+    return run_split_tail(h, ws, base, depth_vals, n, D, H, W, depth, xreg, po, s);
   }
   RUN(3, F(ws.c2), nullptr, F(ws.c3), D / 2, H / 2, W / 2);
   RUN(4, F(ws.c3), nullptr, F(ws.c4), D / 4, H / 4, W / 4);
@@ -2442,7 +2455,7 @@ static int costreg_depth_impl(int in_layout, const v3d_costreg_weights* h, const
   // conv9 + skip + prob on exact-fp32 operands: the tile kernel
   if ((rc = launch_conv9_prob(true, h, F(ws.u8), F(ws.c0), xreg, n, D, H, W, s)) != V3D_OK) return rc;
 #undef RUN
-  return launch_soft_argmin(xreg, depth_vals, depth, n, D, H, W, s);
+  return launch_depth_tail(xreg, depth_vals, depth, po, n, D, H, W, s);
 }
 
 extern "C" int v3d_costreg_depth_f32(const v3d_costreg_weights* h, const float* var, const float* depth_vals, int n,
@@ -2464,6 +2477,42 @@ extern "C" int v3d_costreg_depth_split(const v3d_costreg_weights* h, const void*
                                        size_t workspace_bytes, void* stream) {
   return costreg_depth_impl(1, h, (const float*)var_split, depth_vals, n, D, H, W, depth, reg,
                             V3D_PRECISION_SPLIT_BF16, workspace, workspace_bytes, stream);
+}
+
+// The chain of the three entry points above, the layout and the precision as arguments, and the confidence of the depth beside
+// it (include/v3d.h).  Everything is validated before the first launch.
+extern "C" int v3d_costreg_depth_prob(const v3d_costreg_weights* h, const void* var, int in_layout, int precision,
+                                      const float* depth_vals, double depth_start, double depth_interval, int n, int D, int H,
+                                      int W, float* depth, float* reg, float* prob, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  V3D_REQUIRE(in_layout == V3D_LAYOUT_REFERENCE || in_layout == V3D_LAYOUT_SPLIT || in_layout == V3D_LAYOUT_CL8, V3D_ERR_BAD_ARG,
+              "v3d_costreg_depth_prob: unknown input layout %d", in_layout);
+  const float ds = (float)depth_start, di = (float)depth_interval;
+  V3D_REQUIRE(std::isfinite(ds) && std::isfinite(di) && di != 0.f, V3D_ERR_BAD_ARG,
+              "v3d_costreg_depth_prob: depth_start = %g / depth_interval = %g must be finite fp32 numbers, the interval not zero",
+              depth_start, depth_interval);
+  V3D_REQUIRE(D < (1 << 24), V3D_ERR_BAD_SHAPE, "v3d_costreg_depth_prob: D = %d too large", D);
+  ProbOut po;
+  po.prob = prob; po.depth_start = depth_start; po.depth_interval = depth_interval;
+  return costreg_depth_impl(in_layout, h, (const float*)var, depth_vals, n, D, H, W, depth, reg, precision, workspace,
+                            workspace_bytes, stream, po);
+}
+
+// The last kernel of the chain alone, on a volume the caller holds: soft_argmin_kernel (prob == NULL) or the soft-argmin that also
+// writes the confidence.  Any D, h, w.
+extern "C" int v3d_soft_argmin_f32(const float* x_reg, const float* depth_vals, double depth_start, double depth_interval, int n,
+                                   int D, int H, int W, float* depth, float* prob, void* stream) {
+  V3D_REQUIRE(x_reg && depth_vals && depth, V3D_ERR_BAD_ARG, "v3d_soft_argmin_f32: null argument");
+  V3D_REQUIRE(n > 0 && D > 0 && H > 0 && W > 0 && D < (1 << 24) && (long long)H * W < (1ll << 31) &&
+                  ((long long)n * H * W + 255) / 256 < (1ll << 31),
+              V3D_ERR_BAD_SHAPE, "v3d_soft_argmin_f32: n, D, h, w = %d, %d, %d, %d", n, D, H, W);
+  const float ds = (float)depth_start, di = (float)depth_interval;
+  V3D_REQUIRE(!prob || (std::isfinite(ds) && std::isfinite(di) && di != 0.f), V3D_ERR_BAD_ARG,
+              "v3d_soft_argmin_f32: depth_start = %g / depth_interval = %g must be finite fp32 numbers, the interval not zero",
+              depth_start, depth_interval);
+  ProbOut po;
+  po.prob = prob; po.depth_start = depth_start; po.depth_interval = depth_interval;
+  return launch_depth_tail(x_reg, depth_vals, depth, po, n, D, H, W, (hipStream_t)stream);
 }
 
 #ifdef V3D_PHASE_TIMING

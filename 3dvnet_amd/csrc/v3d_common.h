@@ -241,6 +241,11 @@ int launch_conv0z(bool f32, const void* in, const float* wimg, const float* bias
 int launch_conv12z(const void* c0_split, const float* w1, const float* w2, const float* b1, const float* b2, void* out_split,
                    int n, int D, int H, int W, hipStream_t s);
 
+// soft-argmin that also writes the confidence of its own depth (confidence.hip): x_reg [n, D, H, W] -> depth, prob [n, H, W];
+// the depth has the bits of soft_argmin_kernel (costreg.hip)
+int launch_soft_argmin_prob(const float* xreg, const float* depth_vals, float* depth, float* prob, double depth_start,
+                            double depth_interval, int n, int D, int H, int W, hipStream_t s);
+
 // [n_img, C, HW] -> [n_img, HW, C] (C in {16, 32}); defined in psv_variance.hip
 int transpose_channel_last(const float* feat, float* featT, int n_img, int C, int HW, hipStream_t s);
 

@@ -91,8 +91,10 @@ def gather_pointcloud(pts, pts_feat, pts_batch, sizes=None, group=None):
 
 def process_scene(batch, net, n_src_on_either_side, device, depth_config=None, offsets_list=None,
                   init_depth_batch=None, offset_batch=None, rank=0, world=1,
-                  group=None, gather_depth=True, upsample=False, init_depth_override=None):
-    """Returns the refined depth maps [n_ref, h, w] (all views when gather_depth, else this rank's).
+                  group=None, gather_depth=True, upsample=False, init_depth_override=None, return_prob=False):
+    """Returns the refined depth maps [n_ref, h, w] (all views when gather_depth, else this rank's).  ``return_prob``:
+    ``(all_depth, init_prob)`` -- ``init_prob`` [n_ref, h, w] on the plane grid is the photometric confidence of the stage-1
+    depths (the ``init_prob`` of eval/main.py:92-96), in view order, gathered across ranks exactly as the depth is.
 
     ``n_src_on_either_side``: the reference's k (eval/main.py:36; window ref-k .. ref+k, 2k+1 edges per reference view), or
     a pair ``(n_before, n_after)`` for the one-sided windows of SURVEY.md 8d (cfg2-4: ref-4 .. ref+3 = 1 ref + 7 src); the
@@ -142,6 +144,7 @@ def process_scene(batch, net, n_src_on_either_side, device, depth_config=None, o
         n_local = r1 - r0
         has_feats = getattr(batch, 'features_quarter', None) is not None
         all_depth = torch.empty((n_local, *depth_config['size']), dtype=torch.float32, device=device)
+        init_prob = torch.empty_like(all_depth) if return_prob else None
         feats_local = None          # quarter features of images [r0, r1 + halo)
         half_local = None           # half-resolution features of the same images (stage 3 only, eval-3dvnet.py:36,62)
         # Precomputed features that already live on `device`: the slices ARE the tensors stage 2 / 3 need -- no per-chunk copy
@@ -175,7 +178,11 @@ def process_scene(batch, net, n_src_on_either_side, device, depth_config=None, o
                 if getattr(batch, 'features_half', None) is not None:
                     sl.features_half = batch.features_half[idx_start:idx_end]
             sl.to(device)
-            pred, _, feats_half, feats_quarter, _, _ = net.make_initial_depth_predictions(sl, depth_config)
+            if return_prob:
+                pred, _, feats_half, feats_quarter, _, _, init_prob[c0 - r0:c1 - r0] = \
+                    net.make_initial_depth_predictions(sl, depth_config, return_prob=True)
+            else:
+                pred, _, feats_half, feats_quarter, _, _ = net.make_initial_depth_predictions(sl, depth_config)
             all_depth[c0 - r0:c1 - r0] = pred
             if not dev_feats:
                 if feats_local is None:
@@ -249,12 +256,25 @@ def process_scene(batch, net, n_src_on_either_side, device, depth_config=None, o
                                                    (net.refine_full, imgs)])
         if world > 1 and gather_depth:
             all_depth = all_gather_rows(all_depth, shard_rows, group)
+            if return_prob:
+                init_prob = all_gather_rows(init_prob, shard_rows, group)
         # the back-projection's claim on its workspace (the channel-last copy of THIS scene's features, reused across the
         # sweeps) ends with the scene: it would keep the feature tensor alive until the next call
         ws = getattr(net, '_ws', None)
         if ws is not None and hasattr(ws, 'tags'):
             ws.tags.pop('bp', None)
-        return all_depth
+        return (all_depth, init_prob) if return_prob else all_depth
+
+
+def _pred_config(batch, net):
+    try:
+        device = next(net.parameters()).device
+    except (AttributeError, StopIteration):      # a parameter-free stand-in (the oracle-backed net of the tests)
+        device = batch.rotmats.device
+    cfg = getattr(getattr(net, 'hparams', None), 'depth_test', None)
+    if not (isinstance(cfg, dict) and all(k in cfg for k in ('depth_start', 'depth_interval', 'n_intervals', 'size'))):
+        cfg = DEPTH_CONFIG
+    return device, cfg
 
 
 def pred_func(batch, scene, dset, net):
@@ -265,13 +285,17 @@ def pred_func(batch, scene, dset, net):
     ``preds.npz``).  ``scene`` is unused here as in the reference; ``dset.n_src_on_either_side`` is the window (an int, or a
     ``(before, after)`` pair for this package's one-sided windows); the device is the net's.  Depth / offset configuration:
     ``net.hparams.depth_test`` when it carries the plane-sweep keys, else the script's DEPTH_CONFIG (eval-3dvnet.py:17-23)."""
-    try:
-        device = next(net.parameters()).device
-    except (AttributeError, StopIteration):      # a parameter-free stand-in (the oracle-backed net of the tests)
-        device = batch.rotmats.device
-    cfg = getattr(getattr(net, 'hparams', None), 'depth_test', None)
-    if not (isinstance(cfg, dict) and all(k in cfg for k in ('depth_start', 'depth_interval', 'n_intervals', 'size'))):
-        cfg = DEPTH_CONFIG
+    device, cfg = _pred_config(batch, net)
     depth = process_scene(batch, net, dset.n_src_on_either_side, device, depth_config=cfg, offsets_list=OFFSETS_LIST,
                           upsample=True)
     return depth.detach().cpu().numpy(), None, None
+
+
+def pred_func_with_prob(batch, scene, dset, net):
+    """``pred_func`` that also fills the second slot of the reference's tuple: ``(depth [n_ref, H, W], init_prob [n_ref, h, w],
+    None)``.  ``init_prob`` is the photometric confidence of the stage-1 depths on the plane grid (not the full resolution of
+    the depths: ``fusion.prepare_preds(prob_resize='nearest')`` resizes it); there is no ``final_prob`` for the refined depths."""
+    device, cfg = _pred_config(batch, net)
+    depth, init_prob = process_scene(batch, net, dset.n_src_on_either_side, device, depth_config=cfg, offsets_list=OFFSETS_LIST,
+                                     upsample=True, return_prob=True)
+    return depth.detach().cpu().numpy(), init_prob.detach().cpu().numpy(), None

@@ -184,12 +184,15 @@ def process_depth(ref_depth, ref_image, src_depths, src_images, ref_P, src_Ps, r
     return pts.cpu().numpy(), rgb.cpu().numpy(), valid[0].cpu().numpy()
 
 
-def prepare_preds(preds, out_size=None):
+def prepare_preds(preds, out_size=None, prob_resize=None):
     """Host preparation of a ``preds.npz`` record (``results.write_preds``) for fusion, after
     processresults.py:218-260: 4x4 poses from ``rotmats`` / ``tvecs``; depths zeroed where ``init_prob <= 0.2`` /
     ``final_prob <= 0.1`` when those maps are present; with ``out_size=(H, W)`` different from the depth maps' size the
     depths are nearest-resized and the rows of K rescaled.  ``preds`` is a path or a mapping.  Nothing here touches a
-    device.  -> ``(depths [N, H, W] float32, poses [N, 4, 4] float32, K [N, 3, 3] float32)`` NumPy arrays."""
+    device.  ``prob_resize``: what to do with a probability map whose size differs from the depth maps' (the plane-grid
+    ``init_prob`` of ``eval_3dvnet.pred_func_with_prob`` beside full-resolution depths): ``None`` raises, ``'nearest'`` resizes
+    it with ``F.interpolate(mode='nearest')`` (the reference uses OpenCV's Lanczos-4 there: DESIGN.md 6).
+    -> ``(depths [N, H, W] float32, poses [N, 4, 4] float32, K [N, 3, 3] float32)`` NumPy arrays."""
     if isinstance(preds, (str, bytes)) or hasattr(preds, '__fspath__'):
         with np.load(preds) as f:
             preds = {k: f[k] for k in f.files}
@@ -199,9 +202,14 @@ def prepare_preds(preds, out_size=None):
     poses[:, :3, :3] = np.asarray(preds['rotmats'], dtype=np.float32)
     poses[:, :3, 3] = np.asarray(preds['tvecs'], dtype=np.float32)
     K = np.array(preds['K'], dtype=np.float32)
+    if prob_resize not in (None, 'nearest'):
+        raise ValueError("prepare_preds: prob_resize must be None or 'nearest', got %r" % (prob_resize,))
     for key, thresh in (('init_prob', 0.2), ('final_prob', 0.1)):
         if key in preds and preds[key] is not None:
             p = np.asarray(preds[key])
+            if p.shape != depths.shape and prob_resize == 'nearest' and p.ndim == 3 and p.shape[0] == n:
+                p = F.interpolate(torch.from_numpy(np.ascontiguousarray(p, dtype=np.float32)).unsqueeze(1),
+                                  tuple(depths.shape[-2:]), mode='nearest').squeeze(1).numpy()
             if p.shape != depths.shape:
                 # the reference resizes such a map with OpenCV's Lanczos filter, which this package does not restate
                 raise ValueError('prepare_preds: %s has shape %s, the depth maps %s; resize it before fusing'

@@ -176,9 +176,15 @@ class CostRegNet(nn.Module):
             pass
 
     # -- execution --------------------------------------------------------------------------------
-    def regularize_depth(self, x, depth_vals, return_reg=False, precision=None):
+    def regularize_depth(self, x, depth_vals, return_reg=False, precision=None, return_prob=False, depth_start=None,
+                         depth_interval=None):
         """Rows A5-A6 fused: x [B,Cin,D,h,w] variance volume, depth_vals [D] ->
-        depth [B,h,w] (and x_reg [B,D,h,w] when return_reg).  ``precision`` overrides ``self.precision``."""
+        depth [B,h,w] (and x_reg [B,D,h,w] when return_reg).  ``precision`` overrides ``self.precision``.
+        ``return_prob``: the photometric confidence [B,h,w] of the depth (``utils.get_propability_map`` of softmax(-x_reg) and
+        the depth, written by the soft-argmin kernel itself) is appended to the result; ``depth_start`` / ``depth_interval``
+        then name the grid ``depth_vals`` was built from.  The depth is the same, bit for bit, either way."""
+        if return_prob and (depth_start is None or depth_interval is None):
+            raise ValueError('regularize_depth(return_prob=True) needs depth_start and depth_interval')
         cl8 = isinstance(x, Cl8Variance)
         split = isinstance(x, SplitVariance) and not cl8
         precision = precision or self.precision
@@ -201,6 +207,14 @@ class CostRegNet(nn.Module):
         nbytes = lib.v3d_costreg_workspace_bytes(handle, B, D, h, w)
         ws = self._ws.get('costreg', nbytes, x.device)
         depth_vals = depth_vals.to(device=x.device, dtype=torch.float32).contiguous()
+        if return_prob:
+            prob = torch.empty((B, h, w), dtype=torch.float32, device=x.device)
+            rc = lib.v3d_costreg_depth_prob(handle, _lib.ptr(x), _lib.LAYOUT['cl8' if cl8 else 'split' if split else 'reference'],
+                                            _lib.precision_code(precision), _lib.ptr(depth_vals), float(depth_start),
+                                            float(depth_interval), B, D, h, w, _lib.ptr(depth), _lib.ptr(reg), _lib.ptr(prob),
+                                            _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device))
+            _lib.check(rc, 'v3d_costreg_depth_prob')
+            return (depth, reg, prob) if return_reg else (depth, prob)
         if split or cl8:
             fn = lib.v3d_costreg_depth_cl8 if cl8 else lib.v3d_costreg_depth_split
             rc = fn(handle, _lib.ptr(x), _lib.ptr(depth_vals), B, D, h, w, _lib.ptr(depth),
@@ -409,12 +423,14 @@ class MVSNet(nn.Module):
         return self._depth_vals[key]
 
     def cost_volume_depth(self, features_quarter, batch, depth_start, depth_interval, n_planes,
-                          depth_img_size, return_intermediates=False, csr=None, precision=None, n_ref=None):
+                          depth_img_size, return_intermediates=False, csr=None, precision=None, n_ref=None,
+                          return_prob=False):
         """Rows A1-A6 from quarter-resolution features.  ``precision`` ('split_bf16' | 'fp32') overrides the
         regulariser's ``cnn_3d.precision``.  ``n_ref`` (optional): the number of reference images in ``batch``; with it the
         edge tables are built on the device without the host synchronisation ``torch.unique`` implies (`edges_to_csr`).  With split-bf16 operands, unless the caller asks for the
         intermediates, the variance volume travels to the regulariser in its split-bf16 input format
-        (identical depth, no conversion pass in conv0)."""
+        (identical depth, no conversion pass in conv0).  ``return_prob``: the confidence map [n_ref, h, w] of the depth
+        (`CostRegNet.regularize_depth`) is appended to the result."""
         precision = precision or self.cnn_3d.precision
         split = not return_intermediates and features_quarter.shape[1] == 32 and precision == 'split_bf16'
         # exact fp32: the volume in the channel-last fp32 layout conv0's depth march streams (same numbers as the reference layout).
@@ -432,10 +448,11 @@ class MVSNet(nn.Module):
                                    self.img_size, depth_img_size, workspace=self._ws, csr=csr,
                                    split=split, n_ref=n_ref, cl8=cl8)
         vals = self.depth_values(depth_start, depth_interval, n_planes, var.device)
+        grid = dict(return_prob=True, depth_start=depth_start, depth_interval=depth_interval) if return_prob else {}
         if return_intermediates:
-            depth, reg = self.cnn_3d.regularize_depth(var, vals, return_reg=True, precision=precision)
-            return depth, var, reg
-        return self.cnn_3d.regularize_depth(var, vals, precision=precision)
+            out = self.cnn_3d.regularize_depth(var, vals, return_reg=True, precision=precision, **grid)
+            return (out[0], var) + tuple(out[1:])
+        return self.cnn_3d.regularize_depth(var, vals, precision=precision, **grid)
 
     def check_edges(self):
         """Raise if the edge tables of the most recent forward were rejected by the device builder (``n_ref`` did not match
@@ -444,7 +461,7 @@ class MVSNet(nn.Module):
             self.last_csr.check()
         return self
 
-    def forward(self, batch, depth_start, depth_interval, n_planes, depth_img_size, n_ref=None):
+    def forward(self, batch, depth_start, depth_interval, n_planes, depth_img_size, n_ref=None, return_prob=False):
         if self.feat_extractor is not None:
             # The package's own MnasNet + FPN containers run on the library's backbone kernels (csrc/backbone.hip); a call that
             # does not qualify RAISES -- there is no silent second backend.  The stock PyTorch modules (MIOpen / rocBLAS) are an
@@ -469,6 +486,10 @@ class MVSNet(nn.Module):
             features_half = getattr(batch, 'features_half', None)
             features_quarter = batch.features_quarter
             features_eighth = getattr(batch, 'features_eighth', None)
+        if return_prob:      # the confidence map [n_ref, h, w] of the depth, appended to the reference's tuple
+            depth_img, prob = self.cost_volume_depth(features_quarter, batch, depth_start, depth_interval,
+                                                     n_planes, depth_img_size, n_ref=n_ref, return_prob=True)
+            return depth_img, features_half, features_quarter, features_eighth, prob
         depth_img = self.cost_volume_depth(features_quarter, batch, depth_start, depth_interval,
                                            n_planes, depth_img_size, n_ref=n_ref)
         return depth_img, features_half, features_quarter, features_eighth
@@ -482,17 +503,21 @@ class CostVolumeGraph:
     is required), the workspaces are the module's cached buffers.
 
     The graph reads its inputs from the tensors given at capture time (kept alive here); ``update(...)`` copies new data of the
-    same shapes into them, ``replay()`` runs the step and returns the depth tensor [n_ref, h, w] (the same storage each time).
+    same shapes into them, ``replay()`` runs the step and returns the depth tensor [n_ref, h, w] (the same storage each time);
+    with ``return_prob=True`` the confidence map is captured in the same graph and ``replay()`` returns ``(depth, prob)``.
     No reference counterpart (the reference runs eagerly); results are those of ``MVSNet.cost_volume_depth``, bit for bit."""
 
     def __init__(self, net, features_quarter, batch, depth_start, depth_interval, n_planes, depth_img_size, n_ref,
-                 precision=None, warmup=2):
+                 precision=None, warmup=2, return_prob=False):
         _require_cuda(features_quarter, 'CostVolumeGraph')
         self.net = net
         self.features_quarter = features_quarter
         self.batch = batch
         self._args = (depth_start, depth_interval, n_planes, depth_img_size)
         self._kw = dict(precision=precision, n_ref=int(n_ref))
+        self.prob = None
+        if return_prob:
+            self._kw['return_prob'] = True
         dev = features_quarter.device
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -506,6 +531,8 @@ class CostVolumeGraph:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph), torch.no_grad():
             self.depth = net.cost_volume_depth(features_quarter, batch, *self._args, **self._kw)
+        if return_prob:
+            self.depth, self.prob = self.depth
         # The captured launches carry raw device addresses.  Everything they point to is pinned here: the module's scratch
         # buffers (a later, larger eager call REPLACES the entries of the grow-only workspaces -- the tensors held below stay
         # alive and the graph keeps its own), the cached plane depths, and the identity of the packed weight image, which
@@ -536,4 +563,4 @@ class CostVolumeGraph:
             raise RuntimeError('CostVolumeGraph: the weights of net.cnn_3d changed after capture (the packed weight image '
                                'the graph points to was released); capture a new graph')
         self.graph.replay()
-        return self.depth
+        return self.depth if self.prob is None else (self.depth, self.prob)

@@ -198,6 +198,54 @@ int v3d_costreg_depth_cl8(const v3d_costreg_weights* handle, const void* var_cl8
                           const float* depth_vals, int n_ref, int D, int h, int w, float* depth,
                           float* reg, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Photometric confidence of a plane-sweep depth (additive within ABI version 9; csrc/confidence.hip).
+ * Replaces mv3d/utils.py:111-145 (get_propability_map): the probability mass of the two depth planes that bracket a
+ * pixel's depth on the grid depth_start + i * depth_interval, i in [0, D).
+ *
+ * Plane indices -- all fp32, every operation rounded on its own, depth_start and depth_interval rounded to fp32 first
+ * (as torch rounds a Python scalar that meets an fp32 tensor):
+ *     d = fl(fl(depth - depth_start) / depth_interval)        one subtract, one correctly rounded divide
+ *     l = clamp(floor(d), 0, D - 1),  r = clamp(ceil(d), 0, D - 1)
+ *   l == r rule: when the depth lies exactly on a plane (d is an integer), or below the first / above the last plane (both
+ *     indices clamp to the same end), the SAME value is added twice; the result is 2 p[l] and can reach 2.0.  This is the
+ *     reference's behaviour and is kept.  (The fp32 coordinate of a plane's own depth is not always that plane's integer:
+ *     of torch.linspace(0.5, 5.25, 96) 68 planes land on it, 9 above, 19 below; each follows the rule above as it falls.)
+ *   NaN rule: a d that is NaN or +-infinite (a NaN or infinite depth) is never converted to an integer: l = r = 0, the
+ *     result is 2 p[0].  (x86's float -> int64 conversion, which the reference runs into, gives the same index.)  A finite d
+ *     of any size clamps to 0 or D - 1.
+ * Values:
+ *   v3d_probability_map_f32    cv [n, D, h, w] already holds probabilities: prob = fl(cv[l] + cv[r]).
+ *   v3d_confidence_logits_f32  x_reg [n, D, h, w] holds the regulariser's logits; p = softmax(-x_reg) over D is never
+ *     written: one walk over D keeps the running maximum m of -x and den = sum_d expf(-x_d - m), in the order of operations
+ *     of the soft-argmin (rescaling den by expf(m_old - m_new) whenever the maximum moves), then
+ *     prob = fl(fl(expf(-x[l] - m) / den) + fl(expf(-x[r] - m) / den)): two correctly rounded divides, then one add --
+ *     softmax, gather, add, as the reference orders them.  depth_map [n, h, w] is the caller's.
+ *   v3d_costreg_depth_prob     the chain of v3d_costreg_depth_f32 / _split / _cl8 with the input layout and the precision
+ *     as arguments.  prob == NULL: exactly those entry points (same kernels, same launches).  prob [n_ref, h, w] given: the
+ *     last kernel is the soft-argmin that also writes the confidence of its OWN depth: the depth has the bits of the other
+ *     entry points, prob the bits v3d_confidence_logits_f32 gives for that x_reg and that depth.  depth_start /
+ *     depth_interval describe the grid depth_vals was built from; they are used for the plane indices only.
+ * Every argument is validated on the host before any launch: null pointers and a depth_start / depth_interval that is not
+ * finite as fp32, or a zero interval -> V3D_ERR_BAD_ARG; n, D, h, w <= 0, D >= 2^24 (and for the regulariser D, h, w not
+ * multiples of 8) -> V3D_ERR_BAD_SHAPE.  No workspace besides the regulariser's; repeated launches are bit-identical.
+ * ------------------------------------------------------------------------------------------ */
+#define V3D_LAYOUT_REFERENCE 0 /* fp32 [n_ref, Cin, D, h, w]            (v3d_costreg_depth_f32)   */
+#define V3D_LAYOUT_SPLIT 1     /* v3d_psv_variance_split's hand-off     (v3d_costreg_depth_split) */
+#define V3D_LAYOUT_CL8 2       /* v3d_psv_variance_cl8's fp32 hand-off  (v3d_costreg_depth_cl8)   */
+int v3d_costreg_depth_prob(const v3d_costreg_weights* handle, const void* var, int in_layout, int precision,
+                           const float* depth_vals, double depth_start, double depth_interval, int n_ref, int D, int h,
+                           int w, float* depth, float* reg, float* prob, void* workspace, size_t workspace_bytes,
+                           void* stream);
+/* The last kernel of that chain alone, on an x_reg [n, D, h, w] the caller holds (any D, h, w): depth [n, h, w] = the
+ * soft-argmin; prob NULL: the kernel of v3d_costreg_depth_f32, else the kernel that also writes the confidence. */
+int v3d_soft_argmin_f32(const float* x_reg, const float* depth_vals, double depth_start, double depth_interval, int n, int D,
+                        int h, int w, float* depth, float* prob, void* stream);
+int v3d_confidence_logits_f32(const float* x_reg, const float* depth_map, double depth_start, double depth_interval, int n,
+                              int D, int h, int w, float* prob, void* stream);
+int v3d_probability_map_f32(const float* cv, const float* depth_map, double depth_start, double depth_interval, int n, int D,
+                            int h, int w, float* prob, void* stream);
+
 /* Single dense 3D layer of the regulariser (exposed for per-layer parity tests):
  * layer 0..9 = conv0..conv9 of CostRegNet incl. folded BN + ReLU (+ `skip` added after the ReLU
  * when non-NULL, mvsnet.py:159-161).  in [n, Cin, Di, Hi, Wi] -> out [n, Cout, Do, Ho, Wo].

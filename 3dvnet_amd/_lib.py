@@ -160,6 +160,9 @@ SIGNATURES = {
     'v3d_soft_argmin_f32': (c_int, [c_void_p, c_void_p, c_double, c_double] + [c_int] * 4 + [c_void_p, c_void_p, c_void_p]),
     'v3d_confidence_logits_f32': (c_int, [c_void_p, c_void_p, c_double, c_double] + [c_int] * 4 + [c_void_p, c_void_p]),
     'v3d_probability_map_f32': (c_int, [c_void_p, c_void_p, c_double, c_double] + [c_int] * 4 + [c_void_p, c_void_p]),
+    'v3d_depth_metrics_workspace_bytes': (c_size_t, [c_int] * 3),
+    'v3d_depth_metrics_2d': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int] + [c_int] * 3 +
+                             [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 

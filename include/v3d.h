@@ -726,6 +726,45 @@ int v3d_volume_resample_nearest(const void* src, int elem_bytes, int channels, i
                                 const float* src_origin_host, const float* matrix_host, int align_corners, int nx, int ny, int nz,
                                 const float* dst_origin_host, int fill_outside, const void* fill_host, void* dst, void* stream);
 
+/* 2D depth metrics of predicted depth maps (csrc/depthmetrics.hip): mv3d/eval/metricfunctions.py:26-67 (calc_2d_depth_metrics) as
+ * mv3d/eval/processresults.py:153-169 reaches it (nearest-enlarged predictions, valid = pred != 0 & ~isinf(pred)), in one pass
+ * over the ground truth and without a temporary.  ABI version: STILL 9 -- two new symbols, nothing changed.
+ *   pred [n, hp, wp] fp32; gt [n, H, W] of gt_type 0 (uint16 millimetres), 1 (fp32 metres) or 2 (fp64 metres), aligned to its own
+ *   element only; row_src [H], col_src [W] (DEVICE, int32): the row / column of the prediction that ground-truth row r / column c
+ *   is scored against (the index tables of a nearest resize; entries are clamped to the prediction); both NULL = identity, then
+ *   hp == H and wp == W.  valid_mode 0: every prediction is valid; 1: pred_valid [n, H, W] bytes, non-zero = valid; 2: derived.
+ * Per pixel (i, r, c), float64 with every operation rounded on its own and IEEE division, except where noted:
+ *   g = double(u16) / 1000.0 | the widened fp32 | the fp64;  pf = pred[i, row_src[r], col_src[c]],  p = double(pf);
+ *   pv = true | pred_valid != 0 | (pf != 0 and pf is not +-inf: a NaN prediction is "valid", as in the reference);
+ *   m = pv and g >= 0.5 and g < 65.0;  n_pv += pv;  n_m += m;  and only where m holds:
+ *   e = |p - g|;  q = g + 1e-7;  S_rel += e / q;  S_diff += e;  S_sqrel += (e e) / q;  S_sq += e e;
+ *   t = |double(1.0f / pf) - 1 / g|, the first quotient ONE FP32 DIVISION (the reference's prediction is a float32 tensor where it
+ *   writes 1. / depth_pred; everywhere else the float64 ground truth promotes it first);  S_inv += t, a non-finite t counts as 0;
+ *   c1 += p / g < 1.25 and g / p < 1.25 (the maximum of the two below the bound; a NaN in either counts nothing); c2, c3 likewise
+ *   with 1.5625 and 1.953125.
+ * Per image, the reference's mixed types: denom32 = float(n_m) + 1e-7f (one fp32 addition: 1e-7f for an empty mask, 1 + 2^-23 for
+ * one pixel, n_m otherwise), denom = double(denom32);
+ *   per_image [n, 9] = perc_valid = float(n_pv) / float(H W) (fp32 division), abs_rel = S_rel / denom, abs_diff = S_diff / denom,
+ *   abs_inv = S_inv / denom, sq_rel = S_sqrel / denom, rmse = sqrt(S_sq / denom), d_125 = float(c1) / denom32 (fp32 division),
+ *   d_125_2, d_125_3 likewise; the fp32 values are stored widened.  counts [n, 5] = n_pv, n_m, c1, c2, c3.
+ *   mean [9] = the float64 sum of the rows of per_image in image order, divided by n.
+ * Deviation from the reference: a pixel outside m contributes nothing.  The reference multiplies by a 0 / 1 mask, so one masked
+ * infinite prediction or NaN ground truth turns its sums into NaN; this call returns the metric over the valid pixels.  Non-finite
+ * values inside m propagate by IEEE rules, as there.
+ * Order: no atomics.  An image is cut into slices of 8192 pixels of the flat H W array (a function of H W only); a lane adds groups
+ * of 8 consecutive pixels, chosen by the pixel index alone; lanes are reduced by wave shuffles, waves through LDS, slices go to the
+ * workspace; a second launch of one workgroup sums the slices of each image in slice order and the images in image order.  The
+ * result is bit-identical across launches and devices, and for equal values across the three gt types and any alignment of gt.
+ * Asynchronous on `stream`, allocates nothing, never synchronises.  Host-side errors, before anything is enqueued: V3D_ERR_BAD_ARG
+ * for a null required pointer, one table without the other, a gt_type or valid_mode outside its set, valid_mode 1 without
+ * pred_valid, a gt not aligned to its element; V3D_ERR_BAD_SHAPE for a non-positive size, identity tables with hp != H or wp != W,
+ * H W >= 2^24 (above it the reference's fp32 counts stop being exact); V3D_ERR_WORKSPACE_TOO_SMALL.
+ * v3d_depth_metrics_workspace_bytes returns 0 for a shape the call would reject. */
+size_t v3d_depth_metrics_workspace_bytes(int n, int H, int W);
+int v3d_depth_metrics_2d(const float* pred, int hp, int wp, const int32_t* row_src, const int32_t* col_src, const void* gt,
+                         int gt_type, const uint8_t* pred_valid, int valid_mode, int n, int H, int W, int32_t* counts,
+                         double* per_image, double* mean, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,9 @@ SIGNATURES = {
     'v3d_depth_metrics_workspace_bytes': (c_size_t, [c_int] * 3),
     'v3d_depth_metrics_2d': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int] + [c_int] * 3 +
                              [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'v3d_depth_supervision_workspace_bytes': (c_size_t, [c_int] * 3),
+    'v3d_depth_supervision_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float] +
+                                  [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 

@@ -93,6 +93,8 @@ def build(force=False, verbose=False, strict=False):
             isa_check.check_no_scratch(os.path.join(objdir, 'confidence.o'), 'prob_gather_kernel', strict=strict)
             # 2D depth metrics: the five double sums and five counters of a lane stay in registers across its pixels
             isa_check.check_no_scratch(os.path.join(objdir, 'depthmetrics.o'), 'depth_metrics_[a-z]*_kernel', strict=strict)
+            # depth supervision: the same, with the loss's sum and counter beside them
+            isa_check.check_no_scratch(os.path.join(objdir, 'supervision.o'), 'depth_supervision_[a-z]*_kernel', strict=strict)
         finally:
             sys.path.pop(0)
     if force or procs or linked != tag or _stale(LIB, objs):

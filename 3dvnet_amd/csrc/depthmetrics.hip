@@ -20,12 +20,13 @@
 // at all.  A slice that is not (the base pointer only has to be aligned to its own element: gt[1:] of odd-sized u16 images is
 // 2-byte aligned) and the partial last group are read pixel by pixel, by the same lanes in the same order.
 //
-// Arithmetic per pixel (include/v3d.h states it): float64, every operation rounded on its own (no contraction of e e + S into an
-// FMA), divisions and the square root are the IEEE ones; the one fp32 operation is 1 / p, because the reference's prediction is
-// a float32 tensor there.
+// Arithmetic per pixel (include/v3d.h states it; csrc/depth_pixel.h holds it, shared with csrc/supervision.hip): float64, every
+// operation rounded on its own (no contraction of e e + S into an FMA), divisions and the square root are the IEEE ones; the one
+// fp32 operation is 1 / p, because the reference's prediction is a float32 tensor there.
 #include <cmath>
 #include <cstdint>
 
+#include "depth_pixel.h"
 #include "v3d_common.h"
 
 namespace {
@@ -35,37 +36,12 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kSlice = 8192;      // ground-truth pixels of one image per workgroup: 38 slices of a 480 x 640 image
 constexpr int kGroup = 8;         // consecutive pixels a lane takes per step, whatever their type: 16 bytes of u16, 32 of fp32, 64 of fp64
 
-struct Acc {
-  double rel, diff, inv, sqrel, sq;
-  int pv, m, c1, c2, c3;
-};
+using v3d::depth2d::Acc;          // the per-pixel rule, shared with csrc/supervision.hip
+using v3d::depth2d::pixel;
 
 __device__ __forceinline__ double metres(uint16_t v) { return (double)v / 1000.0; }      // the reference's division
 __device__ __forceinline__ double metres(float v) { return (double)v; }
 __device__ __forceinline__ double metres(double v) { return v; }
-
-__device__ __forceinline__ void pixel(Acc& a, double g, float pf, int valid_mode, uint8_t vbyte) {
-#pragma clang fp contract(off)
-  const double p = (double)pf;
-  const bool pv = valid_mode == 0 ? true : valid_mode == 1 ? vbyte != 0 : (pf != 0.f && fabsf(pf) != INFINITY);   // NaN: valid
-  const bool m = pv && g >= 0.5 && g < 65.0;
-  a.pv += pv;
-  a.m += m;
-  if (m) {
-    const double e = fabs(p - g), q = g + 1e-7;
-    a.rel += e / q;
-    a.diff += e;
-    const double t = fabs((double)(1.0f / pf) - 1.0 / g);
-    a.inv += fabs(t) < (double)INFINITY ? t : 0.0;                 // inf and NaN count as 0
-    const double ee = e * e;
-    a.sqrel += ee / q;
-    a.sq += ee;
-    const double r1 = p / g, r2 = g / p;                           // max(r1, r2) < x  <=>  both < x; a NaN makes it false
-    a.c1 += r1 < 1.25 && r2 < 1.25;
-    a.c2 += r1 < 1.5625 && r2 < 1.5625;
-    a.c3 += r1 < 1.953125 && r2 < 1.953125;
-  }
-}
 
 template <typename GT>
 __global__ __launch_bounds__(kThreads) void depth_metrics_slice_kernel(const float* __restrict__ pred, int hp, int wp,
@@ -122,19 +98,7 @@ __global__ __launch_bounds__(kThreads) void depth_metrics_slice_kernel(const flo
   }
 
   // lanes -> wave (shuffles), waves -> workgroup (LDS, wave order)
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    a.rel += __shfl_down(a.rel, off);
-    a.diff += __shfl_down(a.diff, off);
-    a.inv += __shfl_down(a.inv, off);
-    a.sqrel += __shfl_down(a.sqrel, off);
-    a.sq += __shfl_down(a.sq, off);
-    a.pv += __shfl_down(a.pv, off);
-    a.m += __shfl_down(a.m, off);
-    a.c1 += __shfl_down(a.c1, off);
-    a.c2 += __shfl_down(a.c2, off);
-    a.c3 += __shfl_down(a.c3, off);
-  }
+  v3d::depth2d::wave_reduce(a);
   __shared__ double lds_s[kWaves][5];
   __shared__ int lds_c[kWaves][5];
   const int wave = (int)threadIdx.x >> 6;
@@ -173,20 +137,7 @@ __global__ __launch_bounds__(kThreads) void depth_metrics_finalize_kernel(const 
     }
 #pragma unroll
     for (int k = 0; k < 5; ++k) counts[(size_t)img * 5 + k] = c[k];
-    // the reference's types: the mask's sum is a float32 tensor, + 1e-7 is one fp32 addition; the float64 sums are divided by
-    // its widening, the fp32 counts by itself
-    const float denom32 = (float)c[1] + 1e-7f;
-    const double denom = (double)denom32;
-    double* row = per_image + (size_t)img * 9;
-    row[0] = (double)((float)c[0] / (float)HW);
-    row[1] = s[0] / denom;
-    row[2] = s[1] / denom;
-    row[3] = s[2] / denom;
-    row[4] = s[3] / denom;
-    row[5] = sqrt(s[4] / denom);
-    row[6] = (double)((float)c[2] / denom32);
-    row[7] = (double)((float)c[3] / denom32);
-    row[8] = (double)((float)c[4] / denom32);
+    v3d::depth2d::finish_row(s, c, HW, per_image + (size_t)img * 9);
   }
   __syncthreads();                       // the rows were written by this workgroup: visible to it behind the barrier
   if (threadIdx.x < 9) {

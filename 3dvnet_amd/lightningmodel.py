@@ -1,14 +1,19 @@
-"""Host-side mirror of the inference methods of ``mv3d/lightningmodel.py`` (SURVEY.md §8a rows A7, B2,
+"""Host-side mirror of ``mv3d/lightningmodel.py`` without its training (SURVEY.md §8a rows A7, B2,
 B5, C1-C3; §8b): ``PL3DVNet`` with the reference's constructor arguments, sub-module names and method
-signatures / return tuples.  Training-only members (losses, Lightning hooks, optimiser) are out of
-scope -- the benchmark path runs under ``torch.no_grad()`` (mv3d/eval-3dvnet.py:27).
+signatures / return tuples: the four stage methods, the supervised pass ``forward(batch, offsets, n_iters)``
+with its loss and 2D metrics, ``validation_step`` and ``log_metrics``.  The backward pass, ``training_step``,
+the optimiser and the Lightning hooks are out of scope -- everything here runs without autograd
+(mv3d/eval-3dvnet.py:27).
 """
+import collections
 from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
 
 from . import _lib, utils
+from . import loss as _loss
+from .loss import MAELoss
 from .mvsnet import MVSNet, _Workspace, edges_to_csr
 from .refinement import HypothesisDecoder
 from .scenemodeling import PointNet, SparseUNet
@@ -57,7 +62,9 @@ def backproject_variance(depth_pred, img_feats, rotmats, tvecs, K, ref_src_edges
 
 
 class PL3DVNet(nn.Module):
-    """Reference ``PL3DVNet`` (lightningmodel.py:14-43), inference surface only."""
+    """Reference ``PL3DVNet`` (lightningmodel.py:14-43, 48-282): the stage methods, ``forward`` (the supervised pass: every
+    stage on a batch with ``depth_images``, the MAE loss and the 2D depth metrics at each of its supervised depth maps),
+    ``validation_step`` and ``log_metrics``.  No backward pass: ``training_step`` and ``configure_optimizers`` are absent."""
 
     def __init__(self, depth_train, depth_test, edge_len, feat_dim=16, img_size=(256, 320), hyp_ksize=3,
                  hyp_pad=1, lr=1e-3, lr_step=100, lr_gamma=0.1, finetune=False, feat_extractor=None,
@@ -96,6 +103,10 @@ class PL3DVNet(nn.Module):
         self.refine_quarter = PropagationNet(in_dim=feat_dim + 1, h_dim=32, precision=precision)
         self.refine_half = PropagationNet(in_dim=feat_dim + 1, h_dim=32, precision=precision)
         self.refine_full = PropagationNet(in_dim=3 + 1, h_dim=32, precision=precision)
+        # losses (lightningmodel.py:46): no parameters, no buffers
+        self.mae_loss = MAELoss()
+        self.current_epoch = 0               # Lightning's attribute in the reference; here the caller sets it (weighs the sweep losses)
+        self.logged = None                   # the record of the last log_metrics call
         self._ws = _Workspace()
         self._offset_vals = {}
         self._pts_batch = {}
@@ -221,3 +232,102 @@ class PL3DVNet(nn.Module):
             if add_to_depth:
                 depth_pred.add_(expect.view(n_imgs, *depth_pred.shape[1:]))
         return expect.view(n_imgs, *depth_pred.shape[1:])
+
+    def _supervise(self, depth_pred, depth_gt):
+        """One supervised point of ``forward``: -> (loss_2d, the reference's metric dict), 0-dim float64 device tensors from one
+        kernel pass (3dvnet_amd/loss.py).  The interval is the test configuration's, as in the reference."""
+        sup = _loss.supervise(depth_pred, depth_gt, self.hparams.depth_test['depth_interval'])
+        return sup.mean[_loss.LOSS], _loss.metrics_dict(sup)
+
+    def forward(self, batch, offsets, n_iters, return_depths=False):
+        """lightningmodel.py:48-122: every stage on a batch that carries ``depth_images`` [n_ref, H, W] (fp32 metres, the size of
+        ``batch.images``), with the masked MAE loss and the 2D depth metrics after stage 1, after each of the
+        ``n_iters * len(offsets)`` refinement sweeps and at 1/4, 1/2 and full resolution.  -> the reference's dictionary
+        (``'ref'``, ``'initial'``, ``'loss_2d'``, ``'quarter'``, ``'half'``, ``'final'``, ``'loss'``); every value is a 0-dim
+        float64 device tensor and ``'loss'`` is accumulated in float64 on the device.  ``return_depths`` adds ``'depths'``: clones
+        of the ten (1 + sweeps + 3) supervised depth tensors in order.  Evaluation only: the depth configuration is
+        ``hparams.depth_test`` and nothing here has a backward pass.  Adds no host synchronisation to what the stages do."""
+        if self.training:
+            raise RuntimeError('PL3DVNet.forward: the module is in training mode, but BatchNorm is folded with its running '
+                               'statistics and the HIP kernels have no backward pass; call .eval() first')
+        depth_gt = getattr(batch, 'depth_images', None)
+        if depth_gt is None:
+            raise ValueError('PL3DVNet.forward: the batch carries no depth_images')
+        if getattr(batch, 'images', None) is None:
+            raise ValueError('PL3DVNet.forward: the batch carries no images (the guide of the full-resolution refinement)')
+        if tuple(depth_gt.shape[-2:]) != tuple(batch.images.shape[-2:]):
+            raise ValueError('PL3DVNet.forward: depth_images are %s, images %s; the final supervision needs equal sizes'
+                             % (tuple(depth_gt.shape[-2:]), tuple(batch.images.shape[-2:])))
+        depth_gt = depth_gt.float()
+        out = {'ref': []}
+        depths = []
+
+        def keep(d):
+            if return_depths:
+                depths.append(d.clone())
+
+        # initial depth predictions and their supervision
+        depth_config = self.hparams.depth_test
+        depth_pred, depth_batch, feats_half, feats_quarter, _, ref_idx = self.make_initial_depth_predictions(batch, depth_config)
+        if feats_half is None:
+            raise ValueError('PL3DVNet.forward: no half-resolution features: a network without a backbone needs '
+                             'batch.features_half')
+        csr = self.mvsnet.last_csr
+        depth_pred = depth_pred.contiguous().float()
+        keep(depth_pred)
+        loss_2d, metrics_2d = self._supervise(depth_pred, depth_gt)
+        out['initial'] = metrics_2d
+        out['loss_2d'] = loss_2d
+        loss = torch.zeros((), dtype=torch.float64, device=depth_pred.device) + loss_2d
+
+        _lambda = 1. if self.hparams.finetune else min(self.current_epoch, 10) * 0.1
+
+        for _ in range(n_iters):
+            xs = self.model_scene(depth_pred, depth_batch, feats_quarter, batch.rotmats, batch.tvecs, batch.K,
+                                  batch.ref_src_edges, csr=csr)
+            for offset in offsets:
+                self.run_pointflow(xs, depth_pred, depth_batch, feats_quarter, batch.rotmats, batch.tvecs, batch.K,
+                                   batch.ref_src_edges, offset, 3, csr=csr, add_to_depth=True)
+                keep(depth_pred)
+                # supervise all intermediate predictions
+                loss_offset, metrics = self._supervise(depth_pred, depth_gt)
+                metrics['loss_2d'] = loss_offset
+                loss = loss + _lambda * loss_offset
+                out['ref'].append(metrics)
+
+        # starting size --> 1/4 --> 1/2 --> image size, each supervised
+        for name, net, guide in (('quarter', self.refine_quarter, feats_quarter), ('half', self.refine_half, feats_half),
+                                 ('final', self.refine_full, batch.images)):
+            depth_pred = net.forward_resized(guide[ref_idx], depth_pred)
+            keep(depth_pred)
+            loss_refine, metrics = self._supervise(depth_pred, depth_gt)
+            metrics['loss_2d'] = loss_refine
+            out[name] = metrics
+            loss = loss + loss_refine
+
+        out['loss'] = loss
+        if return_depths:
+            out['depths'] = depths
+        return out
+
+    def log_metrics(self, metrics, prefix='val'):
+        """lightningmodel.py:244-268 without Lightning: the reference's names in its order -> an ordered dictionary of Python
+        floats, returned and kept as ``self.logged`` (this replaces ``self.log``).  One read-back: the values are stacked on the
+        device and copied once."""
+        items = [(prefix + '/loss_2d', metrics['loss_2d']), (prefix + '/loss', metrics['loss'])]
+        items += [(prefix + '_2d/' + k, v) for k, v in metrics['initial'].items()]
+        for key in ('final', 'half', 'quarter'):
+            if key in metrics:
+                items += [('%s_%s/%s' % (prefix, key, k), v) for k, v in metrics[key].items()]
+        for i, metrics_i in enumerate(metrics['ref']):
+            items += [('%s_ref%d/%s' % (prefix, i, k), v) for k, v in metrics_i.items()]
+        dev = metrics['loss'].device
+        vals = torch.stack([torch.as_tensor(v, dtype=torch.float64, device=dev) for _, v in items]).cpu().tolist()
+        self.logged = collections.OrderedDict((name, val) for (name, _), val in zip(items, vals))
+        return self.logged
+
+    def validation_step(self, batch, batch_idx):
+        """lightningmodel.py:279-282"""
+        out = self.forward(batch, [0.05, 0.05, 0.025], 2)
+        self.log_metrics(out, prefix='val')
+        return out['loss']

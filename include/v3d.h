@@ -765,6 +765,34 @@ int v3d_depth_metrics_2d(const float* pred, int hp, int wp, const int32_t* row_s
                          int gt_type, const uint8_t* pred_valid, int valid_mode, int n, int H, int W, int32_t* counts,
                          double* per_image, double* mean, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Depth supervision of PL3DVNet.forward (csrc/supervision.hip): at each point where mv3d/lightningmodel.py:57-119 supervises a depth
+ * map, the masked MAE loss (mv3d/loss.py:6-20) and calc_2d_depth_metrics without a mask, in one pass over the PREDICTION and
+ * without a temporary.  ABI version: STILL 9 -- two new symbols, nothing changed.
+ *   pred [n, h, w] fp32; gt [n, H, W] fp32 metres; row_src [h], col_src [w] (DEVICE, int32): the row / column of the ground truth
+ *   that prediction row r / column c is scored against (the index tables of the nearest resize H -> h, W -> w that the reference
+ *   applies to the ground truth; entries are clamped to the ground truth); both NULL = identity, then H == h and W == w.
+ * Per pixel (i, r, c): gf = gt[i, row_src[r], col_src[c]], g = double(gf), pf = pred[i, r, c], p = double(pf).
+ *   Metrics: the per-pixel rule of v3d_depth_metrics_2d above with valid_mode 0, the same code (csrc/depth_pixel.h): n_pv, n_m,
+ *   S_rel, S_diff, S_inv, S_sqrel, S_sq, c1, c2, c3 with m = g >= 0.5 and g < 65.0, and its deviation (a pixel outside m
+ *   contributes nothing).
+ *   Loss: where gf != 0.0f (an fp32 comparison; a NaN ground truth is in this mask, as in the reference): n_l += 1 and
+ *   S_l += |p - g|, the difference and the sum in float64, every operation rounded on its own.  A non-finite |p - g| is added as it
+ *   is and makes the loss non-finite, as the reference's does.  Pixels with 0 < g < 0.5 or g >= 65 count here and not in m.
+ * Per image: columns 0-8 of per_image [n, 10] are the nine columns of v3d_depth_metrics_2d (perc_valid is 1), counts [n, 6] are
+ *   its five counts and n_l;  per_image[i, 9] = (S_l / double(depth_interval)) / double(float(n_l) + 1e-7f): the reference's
+ *   denominator is a float32 tensor and + 1e-7 one fp32 addition; an image without ground truth gives 0.
+ *   mean [10] = the float64 sum of the rows of per_image in image order, divided by n; mean[9] is the loss.
+ * Order: as v3d_depth_metrics_2d, with slices of 8192 pixels of the flat h w array of the prediction: bit-identical across launches
+ * and devices and for any 4-byte alignment of pred and gt.
+ * Asynchronous on `stream`, allocates nothing, never synchronises.  Host-side errors, before anything is enqueued: V3D_ERR_BAD_ARG
+ * for a null required pointer, one table without the other, pred or gt not aligned to 4 bytes; V3D_ERR_BAD_SHAPE for a
+ * non-positive size, identity tables with H != h or W != w, h w >= 2^24; V3D_ERR_WORKSPACE_TOO_SMALL.
+ * v3d_depth_supervision_workspace_bytes returns 0 for a shape the call would reject. */
+size_t v3d_depth_supervision_workspace_bytes(int n, int h, int w);
+int v3d_depth_supervision_f32(const float* pred, int n, int h, int w, const float* gt, int H, int W, const int32_t* row_src,
+                              const int32_t* col_src, float depth_interval, int32_t* counts, double* per_image, double* mean,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,11 @@ SIGNATURES = {
     'v3d_depth_supervision_workspace_bytes': (c_size_t, [c_int] * 3),
     'v3d_depth_supervision_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float] +
                                   [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'v3d_order_stats_workspace_bytes': (c_size_t, [c_int]),
+    'v3d_backproject_order_stats_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_double), c_int, c_void_p,
+                                                c_void_p, c_void_p, c_size_t, c_void_p]),
+    'v3d_cloud_order_stats_f32': (c_int, [c_void_p, c_int, ctypes.POINTER(c_double), c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                          c_void_p]),
 }
 
 

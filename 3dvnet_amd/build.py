@@ -95,6 +95,8 @@ def build(force=False, verbose=False, strict=False):
             isa_check.check_no_scratch(os.path.join(objdir, 'depthmetrics.o'), 'depth_metrics_[a-z]*_kernel', strict=strict)
             # depth supervision: the same, with the loss's sum and counter beside them
             isa_check.check_no_scratch(os.path.join(objdir, 'supervision.o'), 'depth_supervision_[a-z]*_kernel', strict=strict)
+            # order statistics: the keys of a tile's points and the back-projection stay in registers in every counting pass
+            isa_check.check_no_scratch(os.path.join(objdir, 'order_stats.o'), 'order_stats_[a-z]*_kernel', strict=strict)
         finally:
             sys.path.pop(0)
     if force or procs or linked != tag or _stale(LIB, objs):

@@ -8,6 +8,10 @@ volume with weights and colours (``mv3d/eval/tsdf_atlas.py``: ``TSDFFusion`` :34
   * ``TSDF``                 the holder with ``to`` / ``save`` / ``load`` and the reference's npz keys;
   * ``projection_matrices``  K [R | t] (processresults.py:19-24);
   * ``volume_bounds``        the scene's volume from the quantiles of the back-projected depths (:324-357);
+  * ``volume_bounds_device`` the same volume without the points ever leaving the device or existing in memory
+                             (``csrc/order_stats.hip`` behind ``v3d_backproject_order_stats_f32``: exact order statistics by
+                             radix selection; 52 bytes per batch come back); ``cloud_order_stats`` /
+                             ``backproject_order_stats`` are the thin wrappers.  The drivers take ``bounds='device'``;
   * ``fuse_preds_tsdf``      from a ``preds.npz`` record (path or mapping) to the ``TSDF``;
   * ``TSDF.get_mesh``        the volume -> a ``mesh.TriangleMesh`` on the device (``csrc/mesh.hip``: marching cubes with the
                              project's own case table and the reference's rules around it, tsdf_atlas.py:161-253);
@@ -91,6 +95,136 @@ def volume_bounds(depths, K, poses, vol_prcnt=.995, vol_margin=1.5, vox_res=.04,
         raise ValueError('volume_bounds: no depth map has a usable pixel')
     vol_dim = ((vol_max - origin) / vox_res).int().tolist()
     return origin, vol_max, vol_dim
+
+
+def _order_stats_args(qs, what):
+    qs = [float(q) for q in np.atleast_1d(np.asarray(qs, dtype=np.float64))]
+    if not 1 <= len(qs) <= 4 or not all(0.0 <= q <= 1.0 for q in qs):
+        raise ValueError('%s: one to four quantiles within [0, 1] expected, got %r' % (what, qs))
+    return qs, (ctypes.c_double * len(qs))(*qs)
+
+
+def _order_stats_out(lib, n_q, dev):
+    return (torch.empty(1, dtype=torch.int32, device=dev), torch.empty((n_q, 3, 2), dtype=torch.float32, device=dev),
+            torch.empty(int(lib.v3d_order_stats_workspace_bytes(n_q)), dtype=torch.uint8, device=dev))
+
+
+def cloud_order_stats(pts, qs):
+    """Exact order statistics of a device cloud ``pts`` [N, 3] fp32 for the quantiles ``qs`` (one to four values in [0, 1]) ->
+    ``(count, stats)`` device tensors: ``count`` [1] int32 = the rows without a NaN, ``stats`` [len(qs), 3, 2] fp32 = per
+    quantile and axis the ``lo``-th and ``hi``-th smallest coordinate of the kept rows, ``lo = clamp(floor(q (N - 1)), 0,
+    N - 1)``, ``hi = min(lo + 1, N - 1)`` (float64), as exact input bit patterns; NaN when no row is kept.  Asynchronous: nothing
+    is read back (include/v3d.h: v3d_cloud_order_stats_f32).  No CPU fallback."""
+    lib = _lib.load()
+    pts = torch.as_tensor(pts)
+    if pts.dim() != 2 or pts.shape[1] != 3 or pts.dtype != torch.float32:
+        raise ValueError('cloud_order_stats: pts must be [N, 3] fp32, got %s %s' % (tuple(pts.shape), pts.dtype))
+    qs, q_host = _order_stats_args(qs, 'cloud_order_stats')
+    if not torch.cuda.is_available() or not pts.is_cuda:
+        raise _lib.V3DLibraryError('cloud_order_stats: the cloud must live on a HIP device (no CPU fallback)')
+    pts = pts.contiguous()
+    with torch.cuda.device(pts.device):
+        count, stats, ws = _order_stats_out(lib, len(qs), pts.device)
+        _lib.check(lib.v3d_cloud_order_stats_f32(_lib.ptr(pts), int(pts.shape[0]), q_host, len(qs), _lib.ptr(count), _lib.ptr(stats),
+                                                 _lib.ptr(ws), ws.numel(), _lib.stream_ptr(pts.device)), 'v3d_cloud_order_stats_f32')
+    return count, stats
+
+
+def backproject_order_stats(depths, proj_inv, qs):
+    """``cloud_order_stats`` of the points that ``depths`` [n, h, w] fp32 (device) back-project to through the inverse 4 x 4
+    projections ``proj_inv`` [n, 4, 4] fp32, without the points being stored: pixel (x, y) with depth d becomes
+    ``Pi [x, y, 1, 1 / d]`` de-homogenised, in individually rounded fp32 operations (include/v3d.h:
+    v3d_backproject_order_stats_f32 pins the order).  A zero or NaN depth gives a NaN row, which is dropped.
+    -> ``(count, stats)`` device tensors.  No CPU fallback."""
+    lib = _lib.load()
+    depths, proj_inv = torch.as_tensor(depths), torch.as_tensor(proj_inv)
+    if depths.dim() != 3 or depths.dtype != torch.float32 or tuple(proj_inv.shape) != (depths.shape[0], 4, 4):
+        raise ValueError('backproject_order_stats: depths [n, h, w] fp32 and proj_inv [n, 4, 4] expected, got %s %s and %s'
+                         % (tuple(depths.shape), depths.dtype, tuple(proj_inv.shape)))
+    qs, q_host = _order_stats_args(qs, 'backproject_order_stats')
+    if not torch.cuda.is_available() or not depths.is_cuda:
+        raise _lib.V3DLibraryError('backproject_order_stats: the depths must live on a HIP device (no CPU fallback)')
+    dev = depths.device
+    depths = depths.contiguous()
+    proj_inv = proj_inv.to(dev, torch.float32).contiguous()
+    n, h, w = (int(v) for v in depths.shape)
+    with torch.cuda.device(dev):
+        count, stats, ws = _order_stats_out(lib, len(qs), dev)
+        _lib.check(lib.v3d_backproject_order_stats_f32(_lib.ptr(depths), _lib.ptr(proj_inv), n, h, w, q_host, len(qs), _lib.ptr(count),
+                                                       _lib.ptr(stats), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)),
+                   'v3d_backproject_order_stats_f32')
+    return count, stats
+
+
+def inverse_projections(K, poses):
+    """[N, 3, 3], [N, 4, 4] host tensors -> the [N, 4, 4] fp32 inverses of [K [R | t]; 0 0 0 1], on the host as the reference
+    takes them."""
+    P = projection_matrices(K, poses)
+    last = torch.tensor([[0, 0, 0, 1]]).type_as(P)[None].repeat(P.shape[0], 1, 1)
+    return torch.cat((P, last), dim=1).inverse()
+
+
+def quantile_from_order_stats(count, pair, q):
+    """The pinned finish of a quantile from its two order statistics: ``t = q (N - 1) - lo`` with ``lo = clamp(floor(q (N - 1)),
+    0, N - 1)`` in float64, then ``float32(a + (b - a) t)`` evaluated in float64 (``a`` itself when ``a == b``)."""
+    vi = float(q) * float(count - 1)
+    lo = min(max(np.floor(vi), 0.0), float(count - 1))
+    a, b = np.float64(pair[0]), np.float64(pair[1])
+    if a == b:
+        return np.float32(a)
+    return np.float32(a + (b - a) * np.float64(vi - lo))
+
+
+def volume_bounds_device(depths, K, poses, vol_prcnt=.995, vol_margin=1.5, vox_res=.04, img_batch=100):
+    """``volume_bounds`` with the quantiles taken on the device (same signature, same return triple): per batch of
+    ``img_batch`` views one ``backproject_order_stats`` at ``1 - vol_prcnt`` and ``vol_prcnt`` -- the points are back-projected
+    in registers and never stored -- and, after every batch is enqueued, ONE read-back of ``n_batches x (count + 12 floats)``
+    for the whole scene.  The projections and their 4 x 4 fp32 inverses are formed on the host, as the reference forms them.
+    On the host, per batch, axis and quantile: ``quantile_from_order_stats``, then ``-/+ vol_margin`` and ``.float()`` as the
+    host path; a batch without a point is skipped; running minimum / maximum across batches; ``ValueError`` when no batch has
+    a point.
+
+    The interpolation rule is pinned here and not delegated to ``np.quantile``: NumPy 2.2 computes the virtual index
+    ``q (N - 1)`` in the array's dtype, float32 -- above 2^24 points that rounds the index itself, and on small inputs it moves
+    the result by about 1e-6 relative.  The device path takes the index in float64 and does not inherit that artefact, so its
+    bounds may differ from ``volume_bounds`` in the last bits (the back-projection's rounding order differs from
+    ``torch.bmm``'s as well).  ``depths`` [N, h, w] must live on a HIP device; K and poses are host tensors / arrays.  No CPU
+    fallback: ``V3DLibraryError`` without the library or a device."""
+    _lib.load()
+    depths = torch.as_tensor(depths)
+    if not torch.cuda.is_available() or not depths.is_cuda:
+        raise _lib.V3DLibraryError('volume_bounds_device: the depths must live on a HIP device (no CPU fallback)')
+    K, poses = torch.as_tensor(K).float().cpu(), torch.as_tensor(poses).float().cpu()
+    qs = (1 - vol_prcnt, vol_prcnt)
+    step = int(img_batch)
+    out = []
+    for start in range(0, depths.shape[0], step):
+        Pi = inverse_projections(K[start:start + step], poses[start:start + step])
+        count, stats = backproject_order_stats(depths[start:start + step].float(), Pi, qs)
+        out.append(torch.cat((count, stats.reshape(-1).view(torch.int32))))         # bit patterns: 13 words per batch
+    rec = torch.stack(out).cpu() if out else torch.empty((0, 13), dtype=torch.int32)
+    counts, stats = rec[:, 0].tolist(), rec[:, 1:].contiguous().view(torch.float32).reshape(-1, 2, 3, 2).numpy()
+    origin = vol_max = None
+    for n_kept, st in zip(counts, stats):
+        if n_kept == 0:
+            continue
+        lo = np.array([quantile_from_order_stats(n_kept, st[0, a], qs[0]) for a in range(3)], dtype=np.float32)
+        hi = np.array([quantile_from_order_stats(n_kept, st[1, a], qs[1]) for a in range(3)], dtype=np.float32)
+        lo, hi = torch.as_tensor(lo - vol_margin).float(), torch.as_tensor(hi + vol_margin).float()
+        origin = lo if origin is None else torch.minimum(origin, lo)
+        vol_max = hi if vol_max is None else torch.maximum(vol_max, hi)
+    if origin is None:
+        raise ValueError('volume_bounds_device: no depth map has a usable pixel')
+    vol_dim = ((vol_max - origin) / vox_res).int().tolist()
+    return origin, vol_max, vol_dim
+
+
+def _bounds_fn(bounds, what):
+    if bounds == 'host':
+        return volume_bounds
+    if bounds == 'device':
+        return volume_bounds_device
+    raise ValueError("%s: bounds must be 'host' or 'device', got %r" % (what, bounds))
 
 
 class TSDF:
@@ -418,15 +552,16 @@ def prepare_preds_tsdf(preds, images):
 
 
 def fuse_preds_tsdf(preds, images, vox_res=.04, trunc_ratio=3, vol_prcnt=.995, vol_margin=1.5, img_batch=100, color=True,
-                    device=None, return_fusion=False, gt_mesh=None):
-    """The ``run_tsdf`` branch up to ``get_tsdf()``: bounds from ``volume_bounds``, one ``integrate_batch`` per chunk of
+                    device=None, return_fusion=False, gt_mesh=None, bounds='host'):
+    """The ``run_tsdf`` branch up to ``get_tsdf()``: bounds from ``volume_bounds`` (``bounds='device'``: from
+    ``volume_bounds_device``), one ``integrate_batch`` per chunk of
     ``img_batch`` views, ``get_tsdf()``.  -> ``TSDF`` (on the device); ``return_fusion=True`` -> ``(TSDF, TSDFFusion)``.
     ``gt_mesh``: each chunk's depths are masked with that mesh rendered at the predictions' size before they are integrated
     (:368-371); the bounds are taken from the unmasked depths, as the reference takes them."""
     _lib.load()
     dev = _fusion._device(device)
     depths, poses, K, images = prepare_preds_tsdf(preds, images)
-    origin, _, vol_dim = volume_bounds(depths.to(dev), K, poses, vol_prcnt, vol_margin, vox_res, img_batch)
+    origin, _, vol_dim = _bounds_fn(bounds, 'fuse_preds_tsdf')(depths.to(dev), K, poses, vol_prcnt, vol_margin, vox_res, img_batch)
     fus = TSDFFusion(vol_dim, vox_res, origin, trunc_ratio, dev, color=color, label=False)
     masker = None if gt_mesh is None else _meshtodepth.Renderer(gt_mesh, depths.shape[1], depths.shape[2], device=dev)
     for start in range(0, depths.shape[0], int(img_batch)):
@@ -455,13 +590,14 @@ def _vertex_metrics(vertices, gt_points, voxel_downsample, dist_thresh, dev):
 
 
 def tsdf_mesh_metrics(preds, images, gt_points, vox_res=.04, trunc_ratio=3, voxel_downsample=0.02, dist_thresh=0.05,
-                      vol_prcnt=.995, vol_margin=1.5, img_batch=100, device=None, return_mesh=False, gt_mesh=None):
+                      vol_prcnt=.995, vol_margin=1.5, img_batch=100, device=None, return_mesh=False, gt_mesh=None, bounds='host'):
     """The ``run_tsdf`` branch to its end (processresults.py:297-397) without files: ``fuse_preds_tsdf`` (with ``gt_mesh``: the
     predictions masked by that mesh) -> ``get_mesh`` -> the mesh's vertices through ``metrics3d.voxel_down_sample`` ->
     ``metrics3d.eval_clouds`` against the down-sampled ``gt_points`` [n, 3].  -> the dict of the five metrics and ``'n'`` (the
     number of views); ``return_mesh=True`` -> ``(dict, TriangleMesh)``.  An empty mesh or ground truth gives NaN metrics, as
     the reference's NumPy means do.  The vertices never leave the device; read-backs: the mesh's two counts, the two
-    down-sampled counts and the final 40-byte record (and one status word per rendered chunk with ``gt_mesh``)."""
+    down-sampled counts and the final 40-byte record (and one status word per rendered chunk with ``gt_mesh``).
+    ``bounds`` is ``fuse_preds_tsdf``'s."""
     _lib.load()
     dev = _fusion._device(device)
     if isinstance(preds, (str, bytes)) or hasattr(preds, '__fspath__'):
@@ -469,7 +605,7 @@ def tsdf_mesh_metrics(preds, images, gt_points, vox_res=.04, trunc_ratio=3, voxe
             preds = {k: f[k] for k in f.files}
     n_views = int(np.asarray(preds['depth_preds']).shape[0])
     tsdf = fuse_preds_tsdf(preds, images, vox_res, trunc_ratio, vol_prcnt, vol_margin, img_batch, color=True, device=dev,
-                           gt_mesh=gt_mesh)
+                           gt_mesh=gt_mesh, bounds=bounds)
     mesh = tsdf.get_mesh()
     out = _vertex_metrics(mesh.vertices, gt_points, voxel_downsample, dist_thresh, dev)
     out['n'] = n_views
@@ -477,12 +613,13 @@ def tsdf_mesh_metrics(preds, images, gt_points, vox_res=.04, trunc_ratio=3, voxe
 
 
 def trim_mesh(mesh, poses, K, images=None, size=(480, 640), mask_mesh=None, vox_res=.04, trunc_ratio=3, vol_prcnt=.995,
-              vol_margin=1.5, img_batch=100, device=None):
+              vol_margin=1.5, img_batch=100, device=None, bounds='host'):
     """The reference's ``trim_mesh`` (processresults.py:71-150) over given cameras -- ``poses`` [N, 4, 4] world -> camera, ``K``
     [N, 3, 3] at ``size``: (1) ``meshtodepth.process_scene`` renders the mesh into every view; (2) ``volume_bounds`` of those
     depths; (3) the depths -- with ``mask_mesh`` zeroed where a rendering of that mesh sees nothing (:134-137) -- go into a
     ``TSDFFusion`` in chunks of ``img_batch``, with ``images`` [N, 3, h, w] fp32 as colours (None: a volume without colour);
-    (4) ``get_tsdf().get_mesh()``.  -> ``mesh.TriangleMesh`` on the device: the part of the surface the cameras saw."""
+    (4) ``get_tsdf().get_mesh()``.  -> ``mesh.TriangleMesh`` on the device: the part of the surface the cameras saw.
+    ``bounds='device'`` takes step (2) from ``volume_bounds_device``: the renderings stay on the device."""
     _lib.load()
     dev = _fusion._device(device)
     K, poses = torch.as_tensor(K).float().cpu(), torch.as_tensor(poses).float().cpu()
@@ -494,7 +631,7 @@ def trim_mesh(mesh, poses, K, images=None, size=(480, 640), mask_mesh=None, vox_
                              % ((n, 3, int(size[0]), int(size[1])), tuple(images.shape)))
     renderer = _meshtodepth.Renderer(mesh, size[0], size[1], device=dev)
     depths = torch.cat([renderer.render(K[i:i + step], poses[i:i + step]) for i in range(0, n, step)], dim=0)
-    origin, _, vol_dim = volume_bounds(depths, K, poses, vol_prcnt, vol_margin, vox_res, img_batch)
+    origin, _, vol_dim = _bounds_fn(bounds, 'trim_mesh')(depths, K, poses, vol_prcnt, vol_margin, vox_res, img_batch)
     fus = TSDFFusion(vol_dim, vox_res, origin, trunc_ratio, dev, color=images is not None, label=False)
     masker = None if mask_mesh is None else _meshtodepth.Renderer(mask_mesh, size[0], size[1], device=dev)
     for i in range(0, n, step):
@@ -506,11 +643,11 @@ def trim_mesh(mesh, poses, K, images=None, size=(480, 640), mask_mesh=None, vox_
 
 def mesh_3d_metrics(mesh, gt_points, poses, K, images=None, size=(480, 640), mask_mesh=None, vox_res=.04, trunc_ratio=3,
                     voxel_downsample=0.02, dist_thresh=0.05, vol_prcnt=.995, vol_margin=1.5, img_batch=100, device=None,
-                    return_mesh=False):
+                    return_mesh=False, bounds='host'):
     """The body of ``process_volume_3d_metrics`` (processresults.py:172-200) without files: ``trim_mesh``, then the trimmed
     mesh's vertices and ``gt_points`` down-sampled and scored by ``metrics3d.eval_clouds``.  -> the dict of the five metrics;
-    ``return_mesh=True`` -> ``(dict, trimmed TriangleMesh)``."""
+    ``return_mesh=True`` -> ``(dict, trimmed TriangleMesh)``.  ``bounds`` is ``trim_mesh``'s."""
     dev = _fusion._device(device)
-    trimmed = trim_mesh(mesh, poses, K, images, size, mask_mesh, vox_res, trunc_ratio, vol_prcnt, vol_margin, img_batch, dev)
+    trimmed = trim_mesh(mesh, poses, K, images, size, mask_mesh, vox_res, trunc_ratio, vol_prcnt, vol_margin, img_batch, dev, bounds)
     out = _vertex_metrics(trimmed.vertices, gt_points, voxel_downsample, dist_thresh, dev)
     return (out, trimmed) if return_mesh else out

@@ -793,6 +793,39 @@ int v3d_depth_supervision_f32(const float* pred, int n, int h, int w, const floa
                               const int32_t* col_src, float depth_interval, int32_t* counts, double* per_image, double* mean,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* Exact per-axis order statistics of a 3-D point set (csrc/order_stats.hip): what the volume bounds of a scene take from the
+ * back-projected depths (mv3d/eval/processresults.py:324-357: two quantiles per axis), found by radix selection on the fp32 bit
+ * patterns without the points ever being stored.  ABI version: STILL 9 -- three new symbols, nothing changed.
+ *   v3d_cloud_order_stats_f32        pts [n_pts, 3] fp32 (DEVICE).
+ *   v3d_backproject_order_stats_f32  depths [n, h, w] fp32 and proj_inv [n, 16] (DEVICE): the inverse of the 4 x 4 matrix whose
+ *                         first three rows are K [R | t], row major; ALL 16 entries are used.  Pixel (i, y, x) with d = depths[i, y,
+ *                         x] becomes the point, all fp32, every operation rounded on its own (no fused multiply-add):
+ *                           inv = 1 / d
+ *                           X_r = ((Pi[r][0] x + Pi[r][1] y) + Pi[r][2]) + Pi[r][3] inv     r = 0..3, left to right, x and y the
+ *                                                                                           integer pixel coordinates as floats
+ *                           p_a = X_a / X_3                                                 a = 0, 1, 2
+ *   A row is dropped if and only if at least one of its three coordinates is a NaN (so d == 0 and d == NaN vanish; rows with an
+ *   infinite coordinate stay); it is dropped from all three axes.  N = the rows kept.
+ *   Order: k = bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000) of the fp32 pattern -- monotone over all non-NaN floats, -inf lowest,
+ *   +inf highest, -0.0 just below +0.0.
+ *   Ranks, float64, per q = q_host[j] (HOST, n_q of them, read before the call returns): vi = q (N - 1); lo = clamp(floor(vi), 0,
+ *   N - 1); hi = min(lo + 1, N - 1).
+ *   Outputs (DEVICE): count [1] uint32 = N; stats [n_q, 3, 2] fp32 = per q and axis the lo-th and the hi-th smallest coordinate
+ *   (0-based) as the exact bit pattern of an input value.  N == 0: count = 0 and every entry of stats is a NaN.
+ *   How: three counting passes over the input (digits of 11 + 11 + 10 key bits), each workgroup counting in LDS and adding its
+ *   non-zero bins to the workspace with integer atomics; a one-workgroup kernel between the passes picks each rank's bin.  The
+ *   result does not depend on scheduling: repeated launches are bit-identical.  A workgroup's tile is 2048 points.
+ * Asynchronous on `stream`, allocates nothing, never synchronises; the workspace (at least v3d_order_stats_workspace_bytes(n_q)
+ * bytes, 8-byte aligned) must stay untouched until the work has run.  Host-side errors, before anything is enqueued:
+ * V3D_ERR_BAD_ARG for a null pointer, n_q outside 1..4, a q outside [0, 1] (a NaN included), a misaligned workspace;
+ * V3D_ERR_BAD_SHAPE for a non-positive size or n h w >= 2^31; V3D_ERR_WORKSPACE_TOO_SMALL.  v3d_order_stats_workspace_bytes returns
+ * 0 for an n_q the calls would reject. */
+size_t v3d_order_stats_workspace_bytes(int n_q);
+int v3d_backproject_order_stats_f32(const float* depths, const float* proj_inv, int n, int h, int w, const double* q_host, int n_q,
+                                    uint32_t* count, float* stats, void* workspace, size_t workspace_bytes, void* stream);
+int v3d_cloud_order_stats_f32(const float* pts, int n_pts, const double* q_host, int n_q, uint32_t* count, float* stats,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

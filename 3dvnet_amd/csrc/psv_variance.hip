@@ -50,6 +50,7 @@ struct PsvParams {
   // window kernel, depth walk: a wave owns its 8 pixels for `walk` consecutive chunks of kRDB planes (one depth segment; the
   // last segment of a volume may be shorter)
   int n_dchunk, walk, n_dseg;              // plane chunks per volume, chunks per segment, segments per volume
+  int skip;                                // window kernel: passes whose 64 samples all miss the source image are skipped (developer option "psv_skip")
 };
 
 
@@ -672,6 +673,8 @@ __device__ __forceinline__ int psv_smax(int a, int b) { int r; asm("s_max_i32 %0
 // WALK (depth walk, p.walk > 1): a wave keeps its 8 pixels for p.walk consecutive plane chunks.  WALK = false is the one-chunk
 // kernel as it was before the walk: no chunk loop, and none of what the walk does to stay inside the registers of
 // V3D_PSV_WAVES waves per SIMD (coordinates parked in LDS, values re-derived per chunk behind empty asm statements).
+// Pass skip (p.skip, developer option "psv_skip"): a pass whose 64 samples all fall beside the source image adds exactly zero
+// and keeps only the projection of the next edge (project() has the argument; 19 % of the passes at cfg2, 37 % at cfg5).
 template <bool SPLIT, bool CL8 = false, bool WALK = false>
 __global__ __launch_bounds__(SPLIT ? 64 : 256, V3D_PSV_WAVES) void psv_variance_window_kernel(PsvParams p) {
   static_assert(SPLIT || !CL8, "the channel-last fp32 output uses the single-wave geometry");
@@ -740,11 +743,13 @@ __global__ __launch_bounds__(SPLIT ? 64 : 256, V3D_PSV_WAVES) void psv_variance_
   // per chunk (set at the top of the chunk loop): the lane's world point, and whether its (pixel, plane) exists
   float X, Y, Z;
   bool live1, all_live;
+  unsigned long long live_mask;           // ballot of live1 (wave-uniform)
   const float Wm1 = (float)(p.W - 1), Hm1 = (float)(p.H - 1);
   const float rWm1 = p.rWm1, rHm1 = p.rHm1;
   const float Wfm1 = (float)(p.Wf - 1), Hfm1 = (float)(p.Hf - 1);
   const int Wp = p.Wf + 2;
   const float Wff = (float)p.Wf, Hff = (float)p.Hf;
+  const bool skip_on = p.skip != 0;
 
   // gather role: 8 lanes x float4 per pixel
   const int gpx = lane >> 3;
@@ -799,13 +804,22 @@ __global__ __launch_bounds__(SPLIT ? 64 : 256, V3D_PSV_WAVES) void psv_variance_
   };
   // projection of this lane's (pixel, plane) sample into the source view of edge e (make_taps, spelled out: the cell
   // coordinates are needed): nw cell of the footprint in the bordered map (x0 + 1, y0 + 1) + the four bilinear weights
-  auto project = [&](int e, int& xb, int& yb, f32x4& wq) __attribute__((always_inline)) {
+  auto project = [&](int e, int& xb, int& yb, f32x4& wq, bool& skip) __attribute__((always_inline)) {
     float ix, iy;
     v3d::sample_position(s_P[e % kMaxE], X, Y, Z, Wm1, rWm1, Hm1, rHm1, Wfm1, Hfm1, ix, iy);
     // clamp to [-1, Wf] x [-1, Hf] (make_taps): v_med3_f32 returns the smallest number when an operand is NaN, i.e. -1,
     // what fminf(fmaxf(NaN, -1), Wf) gives
     ix = __builtin_amdgcn_fmed3f(ix, -1.f, Wff);
     iy = __builtin_amdgcn_fmed3f(iy, -1.f, Hff);
+    // Pass skip.  A sample clamped onto -1 or Wf (Hf) lies wholly beside the source image (NaN coordinates clamp to -1): every
+    // cell of its footprint is a border cell (+0) or carries the weight 0, so for finite features its blend sv_ is +-0 (weights
+    // are >= 0).  An accumulator starts at +0 and can never become -0 under round-to-nearest (x + y is -0 only for x = y = -0),
+    // hence acc + (+-0) and fma(+-0, +-0, acc) leave every accumulator bit as it is: a pass whose 64 samples are all such
+    // samples (lanes without a sample count as one) changes nothing and is left out.  The test is exact -- a sample at
+    // -1 < ix < 0 has a weight on column 0 and is not zero -- and wave-uniform: the flag lives in scalar registers.
+    // (four ballots joined in scalar registers: one v_cmp each; __all() of the joined condition goes through a 0 / 1 vector
+    // register and a fifth compare)
+    skip = skip_on && (__ballot(ix != -1.f) & __ballot(ix != Wff) & __ballot(iy != -1.f) & __ballot(iy != Hff) & live_mask) == 0;
     const float x0 = floorf(ix), y0 = floorf(iy);
     const float x1 = x0 + 1.f, y1 = y0 + 1.f;
     const float wx0 = x1 - ix, wx1 = ix - x0, wy0 = y1 - iy, wy1 = iy - y0;
@@ -825,6 +839,7 @@ __global__ __launch_bounds__(SPLIT ? 64 : 256, V3D_PSV_WAVES) void psv_variance_
   // from L2 to LDS (the copy's latency was 0.27 of 1.59 ms when the wave simply waited for it)
   int xb = 0, yb = 0;
   f32x4 wq = {0.f, 0.f, 0.f, 0.f};
+  bool skip = false;                       // wave-uniform: the pass that (xb, yb, wq) belong to adds exactly zero
   if (ne > 0) {
     load_cams(0);
     psv_wave_sync<WPB>();
@@ -847,6 +862,7 @@ __global__ __launch_bounds__(SPLIT ? 64 : 256, V3D_PSV_WAVES) void psv_variance_
       v3d::world_point(s_ref, xf1, yf1, z, X, Y, Z);
     }
     live1 = gp1 < P && d1 < p.D;                              // lane 0 is always live
+    live_mask = __ballot(live1);
     all_live = __all(live1);
 #pragma unroll
     for (int k = 0; k < kRDB; ++k) acc_s[k] = acc_q[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -857,65 +873,71 @@ __global__ __launch_bounds__(SPLIT ? 64 : 256, V3D_PSV_WAVES) void psv_variance_
         load_cams(0);
         psv_wave_sync<WPB>();
       }
-      project(0, xb, yb, wq);
+      project(0, xb, yb, wq, skip);
     }
     for (int e = 0; e < ne; ++e) {
       psv_wave_sync<WPB>();                  // the previous pass is done with s_w / s_slot / s_win
 #ifdef V3D_PSV_NOPIPE                      // developer A/B: project at the top of the pass, wait for the copy right after issuing it
       if (e > 0) {
         if (e % kMaxE == 0) { load_cams(e); psv_wave_sync<WPB>(); }
-        project(e, xb, yb, wq);
+        project(e, xb, yb, wq, skip);
       }
 #endif
-      // Window = the box spanned by the four corner samples (first / last pixel on the first / last plane: a projective map is
-      // monotone in pixel and in depth, so they bound the 64 footprints in all but a few tiles), cut to 16 x 4 cells.  A
-      // sample whose footprint is not inside it is simply marked (bit 0 of its tap word) and takes its cells from featT.
-      int xmin, ymin, ncol, nrow;            // wave-uniform
-      {
-        // (both coordinates of a corner travel in one word: four lane reads instead of eight; bordered coordinates are >= 0)
-        const int cc = (yb << 16) | xb;
-        const int ca = __builtin_amdgcn_readlane(cc, 0), cb = __builtin_amdgcn_readlane(cc, 7);
-        const int cd = __builtin_amdgcn_readlane(cc, 56), ce = __builtin_amdgcn_readlane(cc, 63);
-        const int xa = ca & 0xffff, xc = cb & 0xffff, xd = cd & 0xffff, xe = ce & 0xffff;
-        const int ya = ca >> 16, yc = cb >> 16, yd = cd >> 16, ye = ce >> 16;
-        xmin = psv_smin(psv_smin(xa, xc), psv_smin(xd, xe));
-        ymin = psv_smin(psv_smin(ya, yc), psv_smin(yd, ye));
-        ncol = psv_smax(psv_smax(xa, xc), psv_smax(xd, xe)) - xmin + 2 > 8 ? kWinCols : 8;
-        nrow = psv_smin(psv_smax(psv_smax(ya, yc), psv_smax(yd, ye)) - ymin + 2, kWinRows);
-      }
-      const int base_cell = __builtin_amdgcn_readfirstlane(s_base[e % kMaxE]);
-      const unsigned dx = (unsigned)(xb - xmin), dy = (unsigned)(yb - ymin);
-      const bool inwin = dx <= (unsigned)(ncol - 2) && dy <= (unsigned)(nrow - 2);
-      // tap word: byte offset of the nw cell in the window, or -- sign bit set -- in featT (< 2 GB, checked by the host)
-      const unsigned so_win = ((dy << 4) | dx) * CB;
-      const unsigned so_ext = ((unsigned)(base_cell + __mul24(yb, Wp) + xb) * CB) | 0x80000000u;
-      const unsigned so = inwin ? so_win : so_ext;
-      s_w[lane] = wq;
-      s_slot[lane] = so;
-      // does ANY pixel change its footprint on plane k (bit group k of the ballot)?  plane 0 always loads
-      const unsigned prev = (unsigned)__builtin_amdgcn_ds_bpermute(((lane - 8) & 63) * 4, (int)so);
-      const unsigned long long chg = __ballot(lane < 8 || so != prev);
-      // copy the window: nrow rows of 8 or 16 cells from (xmin, ymin) (runs past the last needed column stay inside the bordered
-      // maps + tail); lane l moves bytes [16 l, 16 l + 16) of each 1 KB run
-      {
-        // wave-uniform row address (SGPR pair) + the lane's 16 bytes (one constant VGPR): no per-lane address arithmetic.  The
-        // copies are written in assembly (hipcc forms 64-bit per-lane addresses for the builtin): M0 = LDS byte address of the
-        // run, saved and restored around each copy; the wave waits for them itself (vmcnt below).
-        const char* rowp = fb + (size_t)((unsigned)(base_cell + ymin * Wp + xmin) * CB);
-        unsigned dst = win_lds;
-        asm volatile("s_nop 4" ::: "memory");            // SGPRs written by v_readlane may feed the first copy's address
-#pragma unroll 1
-        for (int rr = 0; rr < (V3D_PSVW_ABLATE == 3 ? 0 : nrow); ++rr) {
-          unsigned keep;
-          asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                       : "=&s"(keep) : "v"(lane16), "s"(rowp), "s"(dst) : "memory");
-          if (ncol > 8)
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(lane16), "s"(rowp), "s"(dst) : "memory");   // the instruction offset moves BOTH addresses
-          rowp += (size_t)Wp * CB;
-          dst += kWinCols * CB;
+      // A skipped pass (see project()) keeps only the projection of the next edge and the camera reloads: no box, no tap
+      // records, no window copy, no wait, no plane loop.  The mean still divides by ne: the edge counts, its samples are zeros.
+      unsigned long long chg = 0;
+      if (!skip) {
+        // Window = the box spanned by the four corner samples (first / last pixel on the first / last plane: a projective map is
+        // monotone in pixel and in depth, so they bound the 64 footprints in all but a few tiles), cut to 16 x 4 cells.  A
+        // sample whose footprint is not inside it is simply marked (bit 0 of its tap word) and takes its cells from featT.
+        int xmin, ymin, ncol, nrow;            // wave-uniform
+        {
+          // (both coordinates of a corner travel in one word: four lane reads instead of eight; bordered coordinates are >= 0)
+          const int cc = (yb << 16) | xb;
+          const int ca = __builtin_amdgcn_readlane(cc, 0), cb = __builtin_amdgcn_readlane(cc, 7);
+          const int cd = __builtin_amdgcn_readlane(cc, 56), ce = __builtin_amdgcn_readlane(cc, 63);
+          const int xa = ca & 0xffff, xc = cb & 0xffff, xd = cd & 0xffff, xe = ce & 0xffff;
+          const int ya = ca >> 16, yc = cb >> 16, yd = cd >> 16, ye = ce >> 16;
+          xmin = psv_smin(psv_smin(xa, xc), psv_smin(xd, xe));
+          ymin = psv_smin(psv_smin(ya, yc), psv_smin(yd, ye));
+          ncol = psv_smax(psv_smax(xa, xc), psv_smax(xd, xe)) - xmin + 2 > 8 ? kWinCols : 8;
+          nrow = psv_smin(psv_smax(psv_smax(ya, yc), psv_smax(yd, ye)) - ymin + 2, kWinRows);
         }
-      }
+        const int base_cell = __builtin_amdgcn_readfirstlane(s_base[e % kMaxE]);
+        const unsigned dx = (unsigned)(xb - xmin), dy = (unsigned)(yb - ymin);
+        const bool inwin = dx <= (unsigned)(ncol - 2) && dy <= (unsigned)(nrow - 2);
+        // tap word: byte offset of the nw cell in the window, or -- sign bit set -- in featT (< 2 GB, checked by the host)
+        const unsigned so_win = ((dy << 4) | dx) * CB;
+        const unsigned so_ext = ((unsigned)(base_cell + __mul24(yb, Wp) + xb) * CB) | 0x80000000u;
+        const unsigned so = inwin ? so_win : so_ext;
+        s_w[lane] = wq;
+        s_slot[lane] = so;
+        // does ANY pixel change its footprint on plane k (bit group k of the ballot)?  plane 0 always loads
+        const unsigned prev = (unsigned)__builtin_amdgcn_ds_bpermute(((lane - 8) & 63) * 4, (int)so);
+        chg = __ballot(lane < 8 || so != prev);
+        // copy the window: nrow rows of 8 or 16 cells from (xmin, ymin) (runs past the last needed column stay inside the bordered
+        // maps + tail); lane l moves bytes [16 l, 16 l + 16) of each 1 KB run
+        {
+          // wave-uniform row address (SGPR pair) + the lane's 16 bytes (one constant VGPR): no per-lane address arithmetic.  The
+          // copies are written in assembly (hipcc forms 64-bit per-lane addresses for the builtin): M0 = LDS byte address of the
+          // run, saved and restored around each copy; the wave waits for them itself (vmcnt below).
+          const char* rowp = fb + (size_t)((unsigned)(base_cell + ymin * Wp + xmin) * CB);
+          unsigned dst = win_lds;
+          asm volatile("s_nop 4" ::: "memory");            // SGPRs written by v_readlane may feed the first copy's address
+#pragma unroll 1
+          for (int rr = 0; rr < (V3D_PSVW_ABLATE == 3 ? 0 : nrow); ++rr) {
+            unsigned keep;
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                         : "=&s"(keep) : "v"(lane16), "s"(rowp), "s"(dst) : "memory");
+            if (ncol > 8)
+              asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\ts_mov_b32 m0, %0"
+                           : "=&s"(keep) : "v"(lane16), "s"(rowp), "s"(dst) : "memory");   // the instruction offset moves BOTH addresses
+            rowp += (size_t)Wp * CB;
+            dst += kWinCols * CB;
+          }
+        }
+      }      // !skip
+      bool skip_next = false;
 #ifndef V3D_PSV_NOPIPE
       if (e + 1 < ne) {
         if ((e + 1) % kMaxE == 0) {
@@ -923,42 +945,45 @@ __global__ __launch_bounds__(SPLIT ? 64 : 256, V3D_PSV_WAVES) void psv_variance_
           load_cams(e + 1);
           psv_wave_sync<WPB>();
         }
-        project(e + 1, xb, yb, wq);
+        project(e + 1, xb, yb, wq, skip_next);
       }
 #endif
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // the window has landed, the tap records are written
-      psv_wave_sync<WPB>();
-      // deliberately not initialised: the first plane of a pass always loads them
-      f32x4 t00, t01, t10, t11;
-      f32x4 wn = s_w[gpx];
-      unsigned sn = s_slot[gpx];
+      if (!skip) {
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // the window has landed, the tap records are written
+        psv_wave_sync<WPB>();
+        // deliberately not initialised: the first plane of a pass always loads them
+        f32x4 t00, t01, t10, t11;
+        f32x4 wn = s_w[gpx];
+        unsigned sn = s_slot[gpx];
 #pragma unroll
-      for (int pl = 0; pl < kRDB; ++pl) {
-        const f32x4 w = wn;
-        const unsigned so_pl = sn;
-        if (pl + 1 < kRDB) {               // next plane's record: in flight during this plane's blend
-          wn = s_w[(pl + 1) * kRPix + gpx];
-          sn = s_slot[(pl + 1) * kRPix + gpx];
-        }
-        if (((chg >> (8 * pl)) & 0xffull) && (V3D_PSVW_ABLATE != 2 || (pl == 0 && e == 0))) {      // wave-uniform: all pixels reload together (a load costs the same masked or not)
-          // (a wave-uniform test "no sample of this plane is outside the window" -- one ballot per pass -- in front of the per-lane
-          // sign test saves a v_cmp and the exec-mask juggling in 95 % of the planes and measured 0.6 % SLOWER, round 4)
-          if (V3D_PSVW_ABLATE != 6 && (int)so_pl < 0) {
-            const unsigned b00 = so_pl & 0x7fffffffu;
-            t00 = *reinterpret_cast<const f32x4*>(fb + (size_t)(b00 + cgb));
-            t01 = *reinterpret_cast<const f32x4*>(fb + (size_t)(b00 + cgb) + CB);
-            t10 = *reinterpret_cast<const f32x4*>(fb + (size_t)(b00 + rowb));
-            t11 = *reinterpret_cast<const f32x4*>(fb + (size_t)(b00 + rowb) + CB);
-          } else {
-            const char* a = wb + (so_pl + cgb);
-            t00 = *reinterpret_cast<const f32x4*>(a);
-            t01 = *reinterpret_cast<const f32x4*>(a + CB);
-            t10 = *reinterpret_cast<const f32x4*>(a + kWinCols * CB);
-            t11 = *reinterpret_cast<const f32x4*>(a + kWinCols * CB + CB);
+        for (int pl = 0; pl < kRDB; ++pl) {
+          const f32x4 w = wn;
+          const unsigned so_pl = sn;
+          if (pl + 1 < kRDB) {               // next plane's record: in flight during this plane's blend
+            wn = s_w[(pl + 1) * kRPix + gpx];
+            sn = s_slot[(pl + 1) * kRPix + gpx];
           }
+          if (((chg >> (8 * pl)) & 0xffull) && (V3D_PSVW_ABLATE != 2 || (pl == 0 && e == 0))) {      // wave-uniform: all pixels reload together (a load costs the same masked or not)
+            // (a wave-uniform test "no sample of this plane is outside the window" -- one ballot per pass -- in front of the per-lane
+            // sign test saves a v_cmp and the exec-mask juggling in 95 % of the planes and measured 0.6 % SLOWER, round 4)
+            if (V3D_PSVW_ABLATE != 6 && (int)so_pl < 0) {
+              const unsigned b00 = so_pl & 0x7fffffffu;
+              t00 = *reinterpret_cast<const f32x4*>(fb + (size_t)(b00 + cgb));
+              t01 = *reinterpret_cast<const f32x4*>(fb + (size_t)(b00 + cgb) + CB);
+              t10 = *reinterpret_cast<const f32x4*>(fb + (size_t)(b00 + rowb));
+              t11 = *reinterpret_cast<const f32x4*>(fb + (size_t)(b00 + rowb) + CB);
+            } else {
+              const char* a = wb + (so_pl + cgb);
+              t00 = *reinterpret_cast<const f32x4*>(a);
+              t01 = *reinterpret_cast<const f32x4*>(a + CB);
+              t10 = *reinterpret_cast<const f32x4*>(a + kWinCols * CB);
+              t11 = *reinterpret_cast<const f32x4*>(a + kWinCols * CB + CB);
+            }
+          }
+          V3D_PSV_BLEND(pl, w);
         }
-        V3D_PSV_BLEND(pl, w);
-      }
+      }      // !skip
+      skip = skip_next;
     }
 
     // ---- variance -> stores (as in the reuse kernel) -------------------------------------------------------------
@@ -1203,6 +1228,7 @@ static int psv_variance_impl(int mode, const float* feat, const float* K, const 
         // the walking kernel addresses a lane's split / cl8 output slot inside its view's volume with 32 bits
         if ((split || cl8) && 8ull * D * h * w >= (1ull << 32)) p.walk = 1;
         p.n_dseg = ((int)ndc + p.walk - 1) / p.walk;
+        p.skip = v3d::option(v3d::kOptPsvSkip) != 0;
         const unsigned long long nblk = (unsigned long long)n_ref * p.n_dseg * npt;
         wblocks = (unsigned)nblk;
         p.rWm1 = (float)(1.0 / (double)(W - 1));

@@ -55,6 +55,7 @@ enum Option {
   kOptGemmPipe,        // "gemm_pipe": 1 sparse convolutions on the loader / matrix pipeline kernel, 0 the rounds kernel
   kOptPsvWalk,         // "psv_walk": plane chunks a wave of the window kernel walks: 0 auto (by shape), N = N chunks (bit-identical)
   kOptRenderCoop,      // "render_coop": bounding boxes of more than this many pixels are rasterised by the whole wave (bit-identical)
+  kOptPsvSkip,         // "psv_skip": 1 the window kernel skips passes whose samples all miss the source image, 0 never (bit-identical)
   kOptCount
 };
 int option(Option o);

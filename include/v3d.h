@@ -57,8 +57,10 @@ extern "C" {
  *   "psv_walk"        0 | N      plane chunks (of 8 planes) a wave of the window warp kernel walks: chosen from the shape | N (bit-identical)
  *   "render_coop"     N          v3d_mesh_render_depth_f32: bounding boxes of more than N pixels are rasterised by the whole wave,
  *                                smaller ones by the triangle's own thread (default 64; 0 = every box; bit-identical)
- * Unknown names, gemm_rounds / gemm_pipe values other than 0 and 1, and a negative psv_walk / render_coop -> V3D_ERR_BAD_ARG.
- * ("psv_walk" and "render_coop" are additive within ABI version 9: new option names, no changed signature; v3d_version() is not
+ *   "psv_skip"        1 | 0      the window warp kernel skips an (edge, 8 planes, 8 pixels) pass whose samples all fall beside the
+ *                                source image (they add exactly zero) | never skips (bit-identical)
+ * Unknown names, gemm_rounds / gemm_pipe / psv_skip values other than 0 and 1, and a negative psv_walk / render_coop -> V3D_ERR_BAD_ARG.
+ * ("psv_walk", "render_coop" and "psv_skip" are additive within ABI version 9: new option names, no changed signature; v3d_version() is not
  * bumped.) */
 int v3d_set_option(const char* name, int value);
 int v3d_get_option(const char* name, int* value);

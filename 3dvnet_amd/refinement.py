@@ -52,6 +52,13 @@ class HypothesisDecoder(nn.Module):
         return packs, self.net[3].weight.detach().float().contiguous().to(dev), \
             self.net[3].bias.detach().float().contiguous().to(dev)
 
+    def packed_handles(self, device):
+        """(the three v3d_gemm_pack handles of the Conv1d+BN layers, head weight, head bias) on `device`: what
+        v3d_decoder_fused_f32 takes as layers_host / head_weight / head_bias.  Packed once per device and parameter state."""
+        self._dev = torch.device(device)
+        packs, w_last, b_last = self._cache.get(self._build, self._dev)
+        return [pk.handle for pk in packs], w_last, b_last
+
     def features(self, xs, pts, pts_feat, pts_batch):
         """Row C2a: [Nq, n_hyp, in_dim] = [finest level | ... | coarsest level | pts_feat]."""
         lib = _lib.load()

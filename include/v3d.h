@@ -18,6 +18,24 @@
  *     memory is inside weight handles (`v3d_*_pack` / `v3d_*_free`);
  *   - return value: 0 = V3D_OK, negative = error; `v3d_last_error()` returns a thread-local
  *     message.  No C++ exception crosses the boundary.
+ *
+ * Workspace and output contract (enforced per entry point by tests/test_workspace_contract_gpu.py over the table
+ * tests/workspace_cases.py)
+ *   - the contents of every workspace, hash table and output buffer on entry are arbitrary: a call reads no byte of them
+ *     that it, or an earlier call of the same documented chain, has not written.  Every element an entry point is said to
+ *     write is stored, whatever the buffer held;
+ *   - a workspace may be handed to any later call, of any entry point and any shape it is large enough for;
+ *   - no call writes outside `*_workspace_bytes()` / `v3d_hash_bytes()` bytes of its workspace or outside the documented size
+ *     of an output (where a length comes back from the call -- unique keys, compacted points, mesh rows, down-sampled cells --
+ *     rows beyond it are unspecified but inside the buffer);
+ *   - a status word (v3d_edges_csr_status, v3d_voxelize_status, v3d_hash_status, v3d_cloud_status, *status of
+ *     v3d_mesh_render_depth_f32) describes the most recent call on that workspace only: a rejected input leaves nothing behind.
+ *   Exceptions, each stated again at its entry point: buffers a call accumulates into are the caller's state (tsdf / weight /
+ *   color of v3d_tsdf_integrate_f32, `pool` of v3d_gemm_gather_f32, depth_inout of v3d_decoder_fused_f32); a hash table is an
+ *   INPUT of v3d_sparse_neighbors / v3d_sparse_interp_f32 / v3d_decoder_fused_f32; the chains keep what the first call left in
+ *   the workspace -- v3d_voxel_keys -> v3d_voxel_decode / v3d_voxelize_status, v3d_mesh_count_f32 -> v3d_mesh_extract_f32,
+ *   v3d_cloud_downsample_f32 -> v3d_cloud_status, v3d_edges_csr -> v3d_edges_csr_status, and the channel-last feature copy of
+ *   v3d_backproject_variance_f32 for a following call with feat == NULL.
  */
 #ifndef V3D_H_
 #define V3D_H_

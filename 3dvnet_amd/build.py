@@ -97,6 +97,9 @@ def build(force=False, verbose=False, strict=False):
             isa_check.check_no_scratch(os.path.join(objdir, 'supervision.o'), 'depth_supervision_[a-z]*_kernel', strict=strict)
             # order statistics: the keys of a tile's points and the back-projection stay in registers in every counting pass
             isa_check.check_no_scratch(os.path.join(objdir, 'order_stats.o'), 'order_stats_[a-z]*_kernel', strict=strict)
+            # scene batches from frames: the twelve blends of a thread and its table entries stay in registers
+            isa_check.check_no_scratch(os.path.join(objdir, 'frames.o'), 'frames_to_images_kernel', strict=strict)
+            isa_check.check_no_scratch(os.path.join(objdir, 'frames.o'), 'frames_to_depths_kernel', strict=strict)
         finally:
             sys.path.pop(0)
     if force or procs or linked != tag or _stale(LIB, objs):

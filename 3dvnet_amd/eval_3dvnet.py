@@ -13,10 +13,12 @@ points: each rank back-projects its own views and the feature-rich point cloud i
 view order (bit-identical to the single-process tensor), after which voxelise / PointNet / sparse
 U-Net run replicated on every rank.
 """
+import os
+
 import torch
 
 from .batch import Batch
-from . import utils
+from . import results, utils
 from .mvsnet import edges_to_csr
 
 # Reference views per call.  The reference's values (eval-3dvnet.py:12-14: INIT_DEPTH_BATCH = 18, OFFSET_BATCH = 16, "change these
@@ -289,6 +291,23 @@ def pred_func(batch, scene, dset, net):
     depth = process_scene(batch, net, dset.n_src_on_either_side, device, depth_config=cfg, offsets_list=OFFSETS_LIST,
                           upsample=True)
     return depth.detach().cpu().numpy(), None, None
+
+
+def predict_scene(dset, idx, pred_func, net, scene_save_dir, overwrite=False):
+    """The body of the reference's scene loop (mv3d/eval/main.py:46-101) for scene ``idx`` of a ``dataset.Dataset``: build the
+    batch, predict, write ``preds.npz`` into ``scene_save_dir``.  Returns the file's path; when it exists and ``overwrite`` is
+    false nothing is computed.  ``pred_func(batch, scene, dset, net) -> (depth_preds, init_prob, final_prob)`` as above."""
+    scene = dset.scene_dirs[idx]
+    os.makedirs(scene_save_dir, exist_ok=True)
+    pred_file_path = os.path.join(scene_save_dir, 'preds.npz')
+    if os.path.exists(pred_file_path) and not overwrite:
+        return pred_file_path
+    batch, _, _, img_idx = dset.get(idx, return_verbose=True, seed_idx=0)
+    batch.images_batch = torch.zeros(batch.images.shape[0], dtype=torch.long, device=batch.images.device)
+    ref_idx = torch.unique(batch.ref_src_edges[0]).detach().cpu().numpy()
+    depth_preds, init_prob, final_prob = pred_func(batch, scene, dset, net)
+    results.write_preds(pred_file_path, scene, depth_preds, batch, ref_idx, img_idx, init_prob, final_prob)
+    return pred_file_path
 
 
 def pred_func_with_prob(batch, scene, dset, net):

@@ -846,6 +846,42 @@ int v3d_backproject_order_stats_f32(const float* depths, const float* proj_inv, 
 int v3d_cloud_order_stats_f32(const float* pts, int n_pts, const double* q_host, int n_q, uint32_t* count, float* stats,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* Decoded frames -> the tensors of a scene batch (csrc/frames.hip): the device half of mv3d/dsets/dataset.py:75-91 and :159-219,
+ * i.e. crop + cv2.resize(INTER_LINEAR) + the colour normalisation of the colour frames, and the millimetre conversion, the
+ * invalid-depth rule, cv2.resize(INTER_NEAREST) and F.interpolate(mode='nearest') of the depth frames, each as one gather through
+ * index tables the caller computes (3dvnet_amd/dataset.py: PreprocessImage.linear_tables / nearest_tables, in float64 on the
+ * host).  ABI version: STILL 9 -- two new symbols, nothing changed.  Neither call takes scratch memory.
+ *
+ * v3d_frames_to_images_f32
+ *   frames [n, H, W, 3] uint8, interleaved, channel order AS STORED (the reference never swaps OpenCV's BGR and applies mean_rgb[0]
+ *   to the first stored channel); y0, y1 [oh] int32 and wy [oh] fp32: the two source rows of output row r and the weight of the
+ *   second; x0, x1 [ow] and wx [ow] likewise for columns (all six on the DEVICE; an index outside the frame is clamped to it);
+ *   mean_host, std_host: 3 floats each in HOST memory, read before the call returns; images [n, 3, oh, ow] fp32 (the layout
+ *   v3d_stem_block_f32 reads).
+ *   Per output element (i, ch, r, c), with a, b = frames[i, y0[r], x0[c] | x1[c], ch] and c_, d = the same of row y1[r], converted
+ *   to fp32 (exact).  All fp32; every operation below is ONE rounded operation, none of them is fused into a multiply-add, and the
+ *   divisions are IEEE divisions:
+ *     ux = 1 - wx[c];  top = (a * ux) + (b * wx[c]);  bot = (c_ * ux) + (d * wx[c]);
+ *     uy = 1 - wy[r];  v = (top * uy) + (bot * wy[r]);
+ *     quantize != 0:  v = rintf(v)      (round half to even: stands in for the uint8 image cv2.resize hands the reference)
+ *     x = v / 255.0f;  x = x * 255.0f;  x = x / scale_rgb;  x = x - mean[ch];  images[i, ch, r, c] = x / std[ch]
+ *   (that is: three subtractions-from-one, six products and three additions for the blend -- 4 roundings on the path of a value
+ *   through each of the two lerps, 8 in all -- and five for the chain.)
+ * v3d_frames_to_depths_f32
+ *   depth_mm [n, H, W] uint16; ys [oh], xs [ow] int32 (DEVICE): the frame row / column output row r / column c is taken from
+ *   (clamped to the frame); depths [n, oh, ow] fp32:  d = float(depth_mm[i, ys[r], xs[c]]) / 1000.0f (IEEE division);
+ *   depths[i, r, c] = d > 65.0f ? 0 : d  (dataset.py:160-165; its NaN and inf tests cannot fire on converted integers).
+ * Both: asynchronous on `stream`, allocate nothing, never synchronise, every element of the output is written and nothing beside it;
+ * repeated launches are bit-identical.  Host-side errors, before anything is enqueued: V3D_ERR_BAD_ARG for a null pointer, a table
+ * or output not aligned to 4 bytes (depth_mm: 2), a scale_rgb or std that is zero, a non-finite scale_rgb / mean / std;
+ * V3D_ERR_BAD_SHAPE for a non-positive size, 3 n H W >= 2^62 (the kernels index with 64-bit offsets), or an output of 2^31 or more
+ * workgroups (256 threads; a thread writes 4 columns x 3 channels of an image, or one depth). */
+int v3d_frames_to_images_f32(const uint8_t* frames, int n, int H, int W, const int32_t* y0, const int32_t* y1, const float* wy,
+                             const int32_t* x0, const int32_t* x1, const float* wx, int oh, int ow, int quantize, float scale_rgb,
+                             const float* mean_host, const float* std_host, float* images, void* stream);
+int v3d_frames_to_depths_f32(const uint16_t* depth_mm, int n, int H, int W, const int32_t* ys, const int32_t* xs, int oh, int ow,
+                             float* depths, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,11 +1,12 @@
 // Photometric confidence of a plane-sweep depth (mv3d/utils.py:111-145, get_propability_map): the probability mass of the two
 // depth planes that bracket a pixel's depth.
 //
-//   soft_argmin_prob_kernel<true>   the soft-argmin of costreg.hip (same walk over D, same order of operations: the depth has
-//                                   the bits soft_argmin_kernel writes) that keeps the running maximum m and the denominator
-//                                   den at its end, takes the two bracketing planes of its OWN depth, re-reads their two logits
-//                                   and writes their softmax values' sum beside the depth.
-//   soft_argmin_prob_kernel<false>  the same walk for m and den (no numerator) and the same tail on a depth map the caller
+//   soft_argmin_kernel              the regulariser's last kernel: softmax(-x) expectation over the depth planes.
+//   soft_argmin_prob_kernel<true>   the same soft-argmin (one walk function, soft_argmin_walk: the depth has the bits
+//                                   soft_argmin_kernel writes) that keeps the running maximum m and the denominator den at its
+//                                   end, takes the two bracketing planes of its OWN depth, re-reads their two logits and writes
+//                                   their softmax values' sum beside the depth.
+//   soft_argmin_prob_kernel<false>  the walk for m and den alone (no numerator) and the same tail on a depth map the caller
 //                                   gives: the confidence of any depth under the distribution of x_reg.
 //   prob_gather_kernel              the reference's function verbatim on a volume that already holds probabilities.
 //
@@ -19,7 +20,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "v3d_common.h"
+#include "costreg.h"
 
 namespace {
 
@@ -35,6 +36,48 @@ __device__ __forceinline__ void bracket(float depth, float depth_start, float de
   r = finite ? (int)fminf(fmaxf(ceilf(d), 0.f), top) : 0;
 }
 
+// The soft-argmin's walk over the D planes of a pixel's column (mvsnet.py:219-227: p = softmax(-x), depth = sum_d vals[d] p[d])
+// in one pass with a running maximum: m = max_d -x_d, den = sum_d e^{-x_d - m} and, with NUM, num = sum_d vals[d] e^{-x_d - m}.
+// Every soft-argmin kernel of the library walks with this function: the depth is num / den, with and without the confidence.
+template <bool NUM>
+__device__ __forceinline__ void soft_argmin_walk(const float* __restrict__ col, const float* __restrict__ vals, int D, int HW, float& m,
+                                                 float& num, float& den) {
+  m = -INFINITY; num = 0.f; den = 0.f;
+  auto step = [&](float xin, float val) __attribute__((always_inline)) {
+    const float x = -xin;
+    if (x > m) {
+      const float sc = expf(m - x);          // exp(-inf) = 0 on the first plane
+      if (NUM) num *= sc;
+      den *= sc; m = x;
+    }
+    const float ex = expf(x - m);
+    if (NUM) num += val * ex;
+    den += ex;
+  };
+  // 8 planes are requested before the first is consumed (the running-maximum chain is sequential, the loads are not)
+  int d = 0;
+  for (; d + 8 <= D; d += 8) {
+    float x[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x[i] = __builtin_nontemporal_load(col + (size_t)(d + i) * HW);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) step(x[i], NUM ? vals[d + i] : 0.f);
+  }
+  for (; d < D; ++d) step(col[(size_t)d * HW], NUM ? vals[d] : 0.f);
+}
+
+// the soft-argmin alone: x_reg [n, D, HW] -> depth [n, HW]
+__global__ __launch_bounds__(kTile) void soft_argmin_kernel(const float* __restrict__ reg, const float* __restrict__ vals,
+                                                            float* __restrict__ depth, int n, int D, int HW) {
+  const size_t gid = (size_t)blockIdx.x * kTile + threadIdx.x;
+  if (gid >= (size_t)n * HW) return;
+  const int b = gid / HW, pix = gid % HW;
+  float m, num, den;
+  soft_argmin_walk<true>(reg + (size_t)b * D * HW + pix, vals, D, HW, m, num, den);
+  const float e = num / den;
+  depth[gid] = e;
+}
+
 // OWN: depth = the expectation, written to `depth_out` (vals = the plane depths); else depth = depth_in[pixel]
 template <bool OWN>
 __global__ __launch_bounds__(kTile) void soft_argmin_prob_kernel(const float* __restrict__ reg, const float* __restrict__ vals,
@@ -45,28 +88,8 @@ __global__ __launch_bounds__(kTile) void soft_argmin_prob_kernel(const float* __
   if (gid >= (size_t)n * HW) return;
   const int b = gid / HW, pix = gid % HW;
   const float* col = reg + (size_t)b * D * HW + pix;
-  // the walk of soft_argmin_kernel (costreg.hip), statement for statement: num = sum vals_d e^{-x_d - m}, den = sum e^{-x_d - m}
-  float m = -INFINITY, num = 0.f, den = 0.f;
-  auto step = [&](float xin, float val) __attribute__((always_inline)) {
-    const float x = -xin;
-    if (x > m) {
-      const float sc = expf(m - x);          // exp(-inf) = 0 on the first plane
-      if (OWN) num *= sc;
-      den *= sc; m = x;
-    }
-    const float ex = expf(x - m);
-    if (OWN) num += val * ex;
-    den += ex;
-  };
-  int d = 0;
-  for (; d + 8 <= D; d += 8) {
-    float x[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) x[i] = __builtin_nontemporal_load(col + (size_t)(d + i) * HW);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) step(x[i], OWN ? vals[d + i] : 0.f);
-  }
-  for (; d < D; ++d) step(col[(size_t)d * HW], OWN ? vals[d] : 0.f);
+  float m, num, den;
+  soft_argmin_walk<OWN>(col, vals, D, HW, m, num, den);
   float e;
   if (OWN) {
     e = num / den;
@@ -116,6 +139,16 @@ int check_grid(const char* who, double depth_start, double depth_interval, int n
 }  // namespace
 
 namespace v3d {
+
+int launch_soft_argmin(const float* xreg, const float* depth_vals, float* depth, int n, int D, int H, int W, hipStream_t s) {
+  const size_t npix = (size_t)n * H * W;
+  {
+    v3d::TimedScope ts("soft_argmin", s);
+    soft_argmin_kernel<<<(unsigned)((npix + 255) / 256), 256, 0, s>>>(xreg, depth_vals, depth, n, D, H * W);
+  }
+  V3D_CHECK_LAUNCH("soft_argmin_kernel");
+  return V3D_OK;
+}
 
 int launch_soft_argmin_prob(const float* xreg, const float* depth_vals, float* depth, float* prob, double depth_start,
                             double depth_interval, int n, int D, int H, int W, hipStream_t s) {

@@ -1,5 +1,5 @@
 // conv0 of CostRegNet (mvsnet.py:136: ConvBnRelu3d(32 -> 8), k3 p1) on split-bf16 matrix cores, written as a
-// DEPTH MARCH (round 4).  Same arithmetic decomposition as conv0_bf16x2_kernel in costreg.hip -- every fp32 operand
+// DEPTH MARCH (round 4).  Same arithmetic decomposition as conv0_bf16x2_kernel in costreg_conv0.hip -- every fp32 operand
 // x = hi + lo (bf16 pairs), products hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_bf16, fp32 accumulation; MFMA rows =
 // 2 x-shifts x 8 output channels, K = 4 x taps x 8 input channels, the host's weight image [chunk][kz*3+ky][hi, lo][lane][4]
 // is the one that kernel reads -- but the work is laid out differently:
@@ -22,7 +22,7 @@
 #include <utility>
 
 #include "bf16_split.h"
-#include "v3d_common.h"
+#include "costreg.h"
 
 namespace {
 

@@ -1,7 +1,7 @@
 // conv1 + conv2 of CostRegNet (mvsnet.py:137-138: ConvBnRelu3d(8 -> 16, stride 2), ConvBnRelu3d(16 -> 16)) as ONE depth march
 // on split-bf16 matrix cores (round 4; V3D_C12_MARCH=0 selects the two tile kernels instead).  Only conv0, conv2 and conv4 are skip connections:
 // conv1's output is consumed by conv2 alone, so it never has to exist in HBM.  Arithmetic and weight images are those of
-// convg_bf16x2_kernel (costreg.hip: rows = 16 output channels, K = 32 = 4 x taps x 8 input channels with a zero fourth tap,
+// convg_bf16x2_kernel (costreg_convg.hip: rows = 16 output channels, K = 32 = 4 x taps x 8 input channels with a zero fourth tap,
 // hi*hi + hi*lo + lo*hi per product, fp32 accumulation); the two 8-channel chunks of conv2 are summed chunk 0 + chunk 1 (the
 // per-layer kernel runs them through one accumulator: same products, another order).
 //
@@ -29,7 +29,7 @@
 #include <utility>
 
 #include "bf16_split.h"
-#include "v3d_common.h"
+#include "costreg.h"
 
 namespace {
 

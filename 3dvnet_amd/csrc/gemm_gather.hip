@@ -25,6 +25,9 @@
 #include "v3d_common.h"
 #include "gemm_weights.h"
 #include "weight_pack.h"
+#include "phase_timing.h"
+
+PHASE_TIMING_UNIT(v3d_debug_gemm_phase_read)
 
 namespace {
 
@@ -231,30 +234,6 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
     }
   }
 }
-
-#ifdef V3D_PHASE_TIMING
-// developer build only: per-phase cycle counters (wave 0 of every workgroup), see costreg.hip
-constexpr int kPhaseSlots = 1 << 16;
-__device__ unsigned long long g_gg_phase[8 * kPhaseSlots];
-#define PHASE_DECL                                  \
-  long long ph_t = __builtin_readcyclecounter();    \
-  long long ph_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define PHASE_MARK(i)                                   \
-  do {                                                  \
-    long long t_ = __builtin_readcyclecounter();        \
-    ph_acc[i] += t_ - ph_t;                             \
-    ph_t = t_;                                          \
-  } while (0)
-#define PHASE_FLUSH                                                                                      \
-  do {                                                                                                   \
-    if (threadIdx.x == 0 && blockIdx.x < kPhaseSlots)                                                    \
-      for (int i_ = 0; i_ < 8; ++i_) g_gg_phase[blockIdx.x * 8 + i_] = (unsigned long long)ph_acc[i_];   \
-  } while (0)
-#else
-#define PHASE_DECL
-#define PHASE_MARK(i)
-#define PHASE_FLUSH
-#endif
 
 template <int MBW, int NB, bool BF16>
 __global__ __launch_bounds__(256) void gemm_gather_kernel(GemmParams p) {
@@ -764,7 +743,7 @@ __global__ __launch_bounds__(256 + 64 * NL, MINB) void gemm_gather_pipe_kernel(G
     }
 #ifdef V3D_PHASE_TIMING
     if (threadIdx.x == 256 && blockIdx.x < kPhaseSlots)
-      for (int i_ = 4; i_ < 8; ++i_) g_gg_phase[blockIdx.x * 8 + i_] = (unsigned long long)ph_acc[i_];
+      for (int i_ = 4; i_ < 8; ++i_) g_phase[blockIdx.x * 8 + i_] = (unsigned long long)ph_acc[i_];
 #endif
     return;
   }
@@ -840,7 +819,7 @@ __global__ __launch_bounds__(256 + 64 * NL, MINB) void gemm_gather_pipe_kernel(G
   gemm_epilogue<MBW, NB>(p, acc, m0, wave, kq, jn);
 #ifdef V3D_PHASE_TIMING
   if (threadIdx.x == 0 && blockIdx.x < kPhaseSlots)
-    for (int i_ = 0; i_ < 4; ++i_) g_gg_phase[blockIdx.x * 8 + i_] = (unsigned long long)ph_acc[i_];
+    for (int i_ = 0; i_ < 4; ++i_) g_phase[blockIdx.x * 8 + i_] = (unsigned long long)ph_acc[i_];
 #endif
 }
 
@@ -1195,15 +1174,3 @@ extern "C" int v3d_pointnet_input_f32(const float* pts, const float* anchor_pts,
   V3D_CHECK_LAUNCH("pointnet_input_kernel");
   return V3D_OK;
 }
-
-#ifdef V3D_PHASE_TIMING
-extern "C" int v3d_debug_gemm_phase_read(unsigned long long* out8_host, int n_blocks) {
-  V3D_CHECK_HIP(hipDeviceSynchronize());
-  std::vector<unsigned long long> h((size_t)8 * kPhaseSlots);
-  V3D_CHECK_HIP(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_gg_phase), h.size() * sizeof(unsigned long long)));
-  for (int i = 0; i < 8; ++i) out8_host[i] = 0;
-  for (int b = 0; b < n_blocks && b < kPhaseSlots; ++b)
-    for (int i = 0; i < 8; ++i) out8_host[i] += h[(size_t)b * 8 + i];
-  return V3D_OK;
-}
-#endif

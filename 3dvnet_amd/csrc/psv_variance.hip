@@ -23,6 +23,9 @@
 
 #include "bf16_split.h"
 #include "v3d_common.h"
+#include "phase_timing.h"
+
+PHASE_TIMING_UNIT(v3d_debug_psv_phase_read)
 
 namespace {
 
@@ -111,30 +114,6 @@ __global__ __launch_bounds__(256) void transpose_bordered_kernel(const float* __
   }
 }
 
-#ifdef V3D_PHASE_TIMING
-// developer build only: per-phase cycle counters, see costreg.hip
-constexpr int kPhaseSlots = 1 << 16;
-__device__ unsigned long long g_psv_phase[8 * kPhaseSlots];
-#define PHASE_DECL                                  \
-  long long ph_t = __builtin_readcyclecounter();    \
-  long long ph_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define PHASE_MARK(i)                                   \
-  do {                                                  \
-    long long t_ = __builtin_readcyclecounter();        \
-    ph_acc[i] += t_ - ph_t;                             \
-    ph_t = t_;                                          \
-  } while (0)
-#define PHASE_FLUSH                                                                                       \
-  do {                                                                                                    \
-    if (threadIdx.x == 0 && blockIdx.x < kPhaseSlots)                                                     \
-      for (int i_ = 0; i_ < 8; ++i_) g_psv_phase[blockIdx.x * 8 + i_] = (unsigned long long)ph_acc[i_];   \
-  } while (0)
-#else
-#define PHASE_DECL
-#define PHASE_MARK(i)
-#define PHASE_FLUSH
-#endif
-
 // Per-image camera block: [0..8] K^-1, [9..17] R, [18..20] t (used when the image is a reference view) and
 // [24..35] P = K [R|t] (used when it is a source view).
 constexpr int kCamStride = 36;
@@ -201,7 +180,7 @@ __device__ __forceinline__ TapInfo make_taps(float ix, float iy, int Wf, int Hf,
   return ti;
 }
 
-// SPLIT: write the variance as the regulariser's first layer consumes it (costreg.hip, conv0_bf16x2_kernel):
+// SPLIT: write the variance as the regulariser's first layer consumes it (conv0z.hip, conv0z_kernel<false>):
 // every value split x = hi + lo into two bf16, channel-last in 16-byte slots of 8 channels,
 // [n_ref][4 channel groups][hi, lo][D][h][w][8] -- the same 4 bytes per value as fp32, and bit-identical to
 // splitting the fp32 volume later, but conv0 then stages tiles with plain 16-byte copies.
@@ -1319,15 +1298,3 @@ extern "C" int v3d_psv_variance_cl8(const float* feat, const float* K, const flo
   return psv_variance_impl(2, feat, K, R, t, ref_img, edge_ofs, edge_src, n_img, n_ref, n_edges, C, Hf, Wf, H, W,
                            depth_start, depth_interval, D, h, w, var_cl8, workspace, workspace_bytes, stream);
 }
-
-#ifdef V3D_PHASE_TIMING
-extern "C" int v3d_debug_psv_phase_read(unsigned long long* out8_host, int n_blocks) {
-  V3D_CHECK_HIP(hipDeviceSynchronize());
-  std::vector<unsigned long long> h((size_t)8 * kPhaseSlots);
-  V3D_CHECK_HIP(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_psv_phase), h.size() * sizeof(unsigned long long)));
-  for (int i = 0; i < 8; ++i) out8_host[i] = 0;
-  for (int b = 0; b < n_blocks && b < kPhaseSlots; ++b)
-    for (int i = 0; i < 8; ++i) out8_host[i] += h[(size_t)b * 8 + i];
-  return V3D_OK;
-}
-#endif

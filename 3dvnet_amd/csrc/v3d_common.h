@@ -230,23 +230,6 @@ __device__ __forceinline__ void sample_position(const float* Pm, float X, float 
   iy = mul_rn(add_rn(gy, 1.f), mul_rn(0.5f, Hfm1));
 }
 
-// conv0 of CostRegNet as a depth march (conv0z.hip).  f32 = false: split variance volume [n][4][hi, lo][D][H][W] -> split
-// activation [n][hi, lo][D][H][W] (16-byte slots of 8 bf16), `wimg` = the split-bf16 weight image of conv0 (costreg.hip, c0bf).
-// f32 = true: fp32 channel-last volume [n][4][2 halves][D][H][W] (16-byte slots of 4 floats) -> fp32 [n, 8, D, H, W],
-// `wimg` = the fp32 fragment image (c0f32).
-int launch_conv0z(bool f32, const void* in, const float* wimg, const float* bias, void* out, int n, int D, int H, int W,
-                  hipStream_t s);
-
-// conv1 + conv2 of CostRegNet as one depth march (conv12z.hip, experiment): conv0 output [n][hi, lo][D][H][W] (split layout)
-// -> conv2 output [n][2 groups][hi, lo][D2][H2][W2]; `w1` / `w2` = the split-bf16 images of conv1 / conv2 (costreg.hip, cgbf)
-int launch_conv12z(const void* c0_split, const float* w1, const float* w2, const float* b1, const float* b2, void* out_split,
-                   int n, int D, int H, int W, hipStream_t s);
-
-// soft-argmin that also writes the confidence of its own depth (confidence.hip): x_reg [n, D, H, W] -> depth, prob [n, H, W];
-// the depth has the bits of soft_argmin_kernel (costreg.hip)
-int launch_soft_argmin_prob(const float* xreg, const float* depth_vals, float* depth, float* prob, double depth_start,
-                            double depth_interval, int n, int D, int H, int W, hipStream_t s);
-
 // [n_img, C, HW] -> [n_img, HW, C] (C in {16, 32}); defined in psv_variance.hip
 int transpose_channel_last(const float* feat, float* featT, int n_img, int C, int HW, hipStream_t s);
 

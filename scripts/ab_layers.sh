@@ -1,6 +1,6 @@
 # usage: bash scripts/ab_layers.sh  -- sweeps tile configs of the memory-bound conv layers
 run() { # tag, flags
-  touch 3dvnet_amd/csrc/costreg.hip
+  touch 3dvnet_amd/csrc/costreg_fp32.hip
   V3D_EXTRA_FLAGS="$2" python 3dvnet_amd/build.py > /dev/null 2>&1 && python scripts/bench_layers.py --tag "$1" 2>&1 | tail -1 | sed 's/transpose[^|]*psv_variance=[0-9.]* //' | cut -c1-200 || echo "$1 FAILED"
 }
 run base ""
@@ -16,4 +16,4 @@ run L2_4x8x28 "-DV3D_L2_CFG=kConvS1,16,16,4,8,28,8"
 run L2_4x4x28_ck16 "-DV3D_L2_CFG=kConvS1,16,16,4,4,28,16"
 run L8_4x8x28 "-DV3D_L8_CFG=kDeconvS2,32,16,4,8,28,8"
 run L8_4x14x28_o3 "-DV3D_L8_CFG=kDeconvS2,32,16,4,14,28,8,3"
-touch 3dvnet_amd/csrc/costreg.hip; python 3dvnet_amd/build.py > /dev/null
+touch 3dvnet_amd/csrc/costreg_fp32.hip; python 3dvnet_amd/build.py > /dev/null

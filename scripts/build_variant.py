@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Developer: one source compiled with extra flags and linked with the default objects of all the others into
 3dvnet_amd/build/ablate/lib_<tag>.so (scripts that accept V3D_LIB_OVERRIDE load it instead of the default library).
-    python scripts/build_variant.py costreg.hip l9a -DV3D_L9_CFG=kDeconvS2,16,8,4,8,28,16,4"""
+    python scripts/build_variant.py costreg_fp32.hip l9a -DV3D_L9_CFG=kDeconvS2,16,8,4,8,28,16,4"""
 import glob, os, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src, tag, flags = sys.argv[1], sys.argv[2], sys.argv[3:]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Developer tool: phase cycles of conv9_prob_kernel (the last instrumented kernel of the regulariser) from a library whose
-costreg.hip was built with -DV3D_PHASE_TIMING (scripts/build_variant.py; V3D_LIB_OVERRIDE selects it).
+costreg_conv9.hip was built with -DV3D_PHASE_TIMING (scripts/build_variant.py; V3D_LIB_OVERRIDE selects it).
     V3D_LIB_OVERRIDE=3dvnet_amd/build/ablate/lib_x.so python scripts/phase_c9.py --blocks 512"""
 import argparse
 import ctypes
@@ -26,7 +26,7 @@ def main():
     mvs = importlib.import_module('3dvnet_amd.mvsnet')
     Batch = importlib.import_module('3dvnet_amd.batch').Batch
     lib = libm.load()
-    fn = lib.v3d_debug_phase_read
+    fn = lib.v3d_debug_conv9_phase_read
     fn.restype = ctypes.c_int
     fn.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]
     dev = torch.device('cuda:0')

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer tool (library built with -DV3D_PHASE_TIMING, e.g. scripts/build_variant.py costreg.hip phase -DV3D_PHASE_TIMING):
+"""Developer tool (library built with -DV3D_PHASE_TIMING, e.g. scripts/build_variant.py costreg_convg.hip phase -DV3D_PHASE_TIMING):
 average cycles per workgroup and phase of ONE split-bf16 layer (convg / deconvg kernels) at cfg2 shapes.
     V3D_LIB_OVERRIDE=3dvnet_amd/build/ablate/lib_phase.so python scripts/phase_convg.py --layer 2 [--refs 64]"""
 import argparse, ctypes, importlib, os, sys
@@ -16,7 +16,7 @@ if os.environ.get('V3D_LIB_OVERRIDE'):
 syn = importlib.import_module('3dvnet_amd.synthetic')
 mvs = importlib.import_module('3dvnet_amd.mvsnet')
 lib = libm.load()
-fn = lib.v3d_debug_phase_read
+fn = lib.v3d_debug_convg_phase_read
 fn.restype = ctypes.c_int
 fn.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]
 dev = torch.device('cuda:0')

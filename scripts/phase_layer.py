@@ -26,7 +26,8 @@ def main():
     syn = importlib.import_module('3dvnet_amd.synthetic')
     mvs = importlib.import_module('3dvnet_amd.mvsnet')
     lib = libm.load()
-    fn = lib.v3d_debug_phase_read
+    # the per-layer entry point runs costreg_fp32.hip, or (conv0 in split-bf16 precision) costreg_conv0.hip
+    fn = lib.v3d_debug_conv0_phase_read if args.layer == 0 and args.precision == 'split_bf16' else lib.v3d_debug_fp32_phase_read
     fn.restype = ctypes.c_int
     fn.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]
     dev = torch.device('cuda:0')

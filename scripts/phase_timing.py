@@ -28,7 +28,7 @@ def main():
     libm = importlib.import_module('3dvnet_amd._lib')
     Batch = importlib.import_module('3dvnet_amd.batch').Batch
     lib = libm.load()
-    fn = lib.v3d_debug_phase_read
+    fn = lib.v3d_debug_conv9_phase_read      # the chain's conv9 + prob kernel (costreg_conv9.hip)
     fn.restype = ctypes.c_int
     fn.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]
     dev = torch.device('cuda:0')

@@ -1087,7 +1087,7 @@ CASES.append(Case(
     sections=lambda lib, i: {'psv': lib.v3d_psv_workspace_bytes(i['n_img'], 32, 16, 20)},
     groups=lambda i: [('warp kernel: tiles of 8 pixels, per view and chunk of 8 planes', i['h'] * i['w'], 8,
                        np.unique(i['edges'][0]).size * -(-i['D'] // 8))],
-    constants=(('kRPix = 8', 'psv_variance.hip:410'), ('8 planes x 8 pixels = 64 lanes', 'psv_variance.hip:684')), rule_on='big'))
+    constants=(('kRPix = 8', 'psv_variance.hip:389'), ('8 planes x 8 pixels = 64 lanes', 'psv_variance.hip:663')), rule_on='big'))
 
 
 _NETS = {}
@@ -1112,7 +1112,7 @@ def _reg_make(size):
         d0, dd, D = g['depth_cfg']
         return dict(var=g['var'], d0=float(d0), dd=float(dd), D=int(D), cin=32)
     rng = np.random.default_rng(5 if size == 'big' else 6)
-    n, cin, D, h, w = {'big': (2, 32, 16, 8, 24), 'c16': (1, 16, 8, 8, 8)}[size]   # c16: in_channels / 8 = ngrp < 4 (costreg.hip:2438)
+    n, cin, D, h, w = {'big': (2, 32, 16, 8, 24), 'c16': (1, 16, 8, 8, 8)}[size]   # c16: in_channels / 8 = ngrp < 4 (costreg.hip:256)
     return dict(var=(rng.random((n, cin, D, h, w)) ** 2 * 0.2).astype(np.float32), d0=0.5, dd=0.125, D=D, cin=cin)
 
 
@@ -1193,7 +1193,7 @@ for _entry, _sym, _extra in (('f32', 'v3d_costreg_depth_f32', ('c16',)), ('split
               '1e-6 of confidence_oracle.logits_f32 (tests/test_costvolume_gpu.py, tests/test_confidence_gpu.py)',
         sections=None,                                                         # v3d_costreg_workspace_bytes takes a weight handle: needs a device
         groups=_reg_groups,
-        constants=(('soft_argmin_kernel<<<(unsigned)((npix + 255) / 256), 256', 'costreg.hip:2293'),
+        constants=(('soft_argmin_kernel<<<(unsigned)((npix + 255) / 256), 256', 'confidence.hip:147'),
                    ('(D, h, w divisible by 8)', 'include/v3d.h:201')), extra=_extra, rule_on='big'))
 
 
@@ -1227,7 +1227,7 @@ CASES.append(Case(
     bound='oracle.costvolume.conv_bn_relu3d within 4e-5 of max|out| (tests/test_costvolume_gpu.py::test_costreg_single_layers_split_kernels)',
     sections=lambda lib, i: {'layer_split': lib.v3d_costreg_layer_split_workspace_bytes(*[int(v) for v in i['x'].shape])},
     groups=lambda i: [('re-encode + conv2 tiles: voxels per view', 6 * 10 * 18, 256, i['n'])],
-    constants=(('encode_split_kernel<<<(unsigned)((total + 255) / 256), 256', 'costreg.hip:2251'),)))
+    constants=(('encode_split_kernel<<<(unsigned)((total + 255) / 256), 256', 'costreg_convg.hip:579'),)))
 
 
 # ---- the fused hypothesis decoder and the fused inverted-residual block ---------------------------------------------------------------

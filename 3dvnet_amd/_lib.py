@@ -174,6 +174,8 @@ SIGNATURES = {
     'v3d_frames_to_images_f32': (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 6 + [c_int, c_int, c_int, c_float, c_float_p,
                                          c_float_p, c_void_p, c_void_p]),
     'v3d_frames_to_depths_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    'v3d_register_colour_u8': (c_int, [c_void_p, c_int, c_int, c_int, c_float_p, c_int, c_int, c_void_p, c_void_p]),
+    'v3d_lut_u16': (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -100,6 +100,9 @@ def build(force=False, verbose=False, strict=False):
             # scene batches from frames: the twelve blends of a thread and its table entries stay in registers
             isa_check.check_no_scratch(os.path.join(objdir, 'frames.o'), 'frames_to_images_kernel', strict=strict)
             isa_check.check_no_scratch(os.path.join(objdir, 'frames.o'), 'frames_to_depths_kernel', strict=strict)
+            # scene preparation: the four sample positions and the twelve bytes of a thread stay in registers
+            isa_check.check_no_scratch(os.path.join(objdir, 'prepare.o'), 'register_colour_kernel', strict=strict)
+            isa_check.check_no_scratch(os.path.join(objdir, 'prepare.o'), 'lut_u16_kernel', strict=strict)
         finally:
             sys.path.pop(0)
     if force or procs or linked != tag or _stale(LIB, objs):

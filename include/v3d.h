@@ -882,6 +882,44 @@ int v3d_frames_to_images_f32(const uint8_t* frames, int n, int H, int W, const i
 int v3d_frames_to_depths_f32(const uint16_t* depth_mm, int n, int H, int W, const int32_t* ys, const int32_t* xs, int oh, int ow,
                              float* depths, void* stream);
 
+/* Raw scenes -> prepared scene folders, the pixel half (csrc/prepare.hip): the registration of a colour frame into the depth
+ * camera (data_preprocess/preprocess_scannet.py:36-70) and the depth-unit conversion of the TUM-format datasets
+ * (preprocess_icl_nuim.py:181-185, preprocess_tum_rgbd.py:177-180).  ABI version: STILL 9 -- two new symbols, nothing changed.
+ * Neither call takes scratch memory.
+ *
+ * v3d_register_colour_u8
+ *   colour [n, Hc, Wc, 3] uint8, interleaved, channel order AS STORED; homography_host: the nine fp32 entries H00 .. H22 of
+ *   K_color K_depth^-1, row major, in HOST memory, read before the call returns (one matrix serves the call: a scene has one pair
+ *   of intrinsics); out [n, h, w, 3] uint8.
+ *   Per output pixel (i, y, x), x and y the integer pixel coordinates as floats.  All fp32; every operation below is ONE rounded
+ *   operation, none of them is fused into a multiply-add, and the divisions are IEEE divisions:
+ *     u = ((H00 x) + (H01 y)) + H02;   v = ((H10 x) + (H11 y)) + H12;   d = ((H20 x) + (H21 y)) + H22;
+ *     d = d + 1e-8f;   u = u / d;   v = v / d;
+ *     gx = (u - Wc / 2) / (Wc / 2);   gy = (v - Hc / 2) / (Hc / 2)        (the reference's normalisers, NOT those of
+ *                                     align_corners=True: the sample lands at u (Wc - 1) / Wc.  Kept as the reference has it.)
+ *     ix = (gx + 1) * ((Wc - 1) / 2);   iy = (gy + 1) * ((Hc - 1) / 2)    (grid_sample's un-normalisation with align_corners=True,
+ *                                     in the form of ATen's CPU kernel; Wc / 2, Hc / 2, (Wc - 1) / 2 and (Hc - 1) / 2 are fp32
+ *                                     constants formed once)
+ *     jx = rintf(ix);   jy = rintf(iy)                                    (round half to even)
+ *     out[i, y, x, :] = colour[i, jy, jx, :] where 0 <= jx < Wc and 0 <= jy < Hc; three zero bytes where (jx, jy) lies outside the
+ *     frame or a coordinate is not finite (such a pixel reads nothing).
+ *   A thread writes four consecutive pixels of a row: three dword stores where w % 4 == 0 and out is 4-byte aligned, byte stores
+ *   otherwise; the two give the same bytes.
+ * v3d_lut_u16
+ *   out[i] = lut[in[i]] for i < n_elems; in, out [n_elems] uint16, lut [65536] uint16, all on the DEVICE; out must not overlap in.
+ *   The depth-unit conversion: the two reference scripts convert in float64 and in float32 and disagree on 144 of the 65 536
+ *   inputs, so the caller evaluates the reference's expression in the reference's type once per input value
+ *   (3dvnet_amd/preprocess.py: depth_lut) and the kernel holds no arithmetic.  16-byte loads and stores where in and out are
+ *   16-byte aligned, element by element otherwise; the two give the same values.
+ * Both: asynchronous on `stream`, allocate nothing, never synchronise, every element of the output is written and nothing beside it;
+ * the inputs are only read; repeated launches are bit-identical.  Host-side errors, before anything is enqueued: V3D_ERR_BAD_ARG for
+ * a null pointer, an in / lut / out of v3d_lut_u16 not aligned to 2 bytes; V3D_ERR_BAD_SHAPE for a non-positive size, 3 n Hc Wc >=
+ * 2^62 (the kernels index with 64-bit offsets), or a launch of 2^31 or more workgroups (256 threads; a thread writes 4 pixels, or 8
+ * elements of an aligned / 1 of an unaligned v3d_lut_u16). */
+int v3d_register_colour_u8(const uint8_t* colour, int n, int Hc, int Wc, const float* homography_host, int h, int w, uint8_t* out,
+                           void* stream);
+int v3d_lut_u16(const uint16_t* in, size_t n_elems, const uint16_t* lut, uint16_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -176,6 +176,8 @@ SIGNATURES = {
     'v3d_frames_to_depths_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'v3d_register_colour_u8': (c_int, [c_void_p, c_int, c_int, c_int, c_float_p, c_int, c_int, c_void_p, c_void_p]),
     'v3d_lut_u16': (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    'v3d_psv_variance_backward_f32': (c_int, [c_void_p] * 7 + [c_int] * 8 + [c_double] * 2 + [c_int] * 3 +
+                                      [c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -22,7 +22,7 @@
 #include <vector>
 
 #include "bf16_split.h"
-#include "v3d_common.h"
+#include "psv_common.h"
 #include "phase_timing.h"
 
 PHASE_TIMING_UNIT(v3d_debug_psv_phase_read)
@@ -114,43 +114,48 @@ __global__ __launch_bounds__(256) void transpose_bordered_kernel(const float* __
   }
 }
 
-// Per-image camera block: [0..8] K^-1, [9..17] R, [18..20] t (used when the image is a reference view) and
-// [24..35] P = K [R|t] (used when it is a source view).
-constexpr int kCamStride = 36;
+// Sample geometry.  The camera block of an image (cam_block: K^-1, R, t, P = K [R|t]), the plane-sweep grid (psv_grid_coord,
+// psv_plane_depth) and the footprint of a sample position (psv_footprint: clamp, nw cell, the four weights) are stated once, in
+// psv_common.h, beside v3d::world_point / v3d::sample_position of v3d_common.h: the backward of this operation
+// (psv_backward.hip) calls the same functions and so samples at the same positions, bit for bit.
+// Per-image camera blocks, one thread per image:
+using v3d::kCamStride;
 
 __global__ void cam_setup_kernel(const float* __restrict__ K, const float* __restrict__ R,
                                  const float* __restrict__ t, float* __restrict__ camp, int n_img) {
   const int img = blockIdx.x * blockDim.x + threadIdx.x;
   if (img >= n_img) return;
-  const float* Kp = K + img * 9;
-  const float* Rp = R + img * 9;
-  const float* tp = t + img * 3;
-  float* o = camp + img * kCamStride;
-  // K^-1 in fp64 (adjugate / determinant), rounded to f32 (utils.py:103 torch.inverse)
-  double a = Kp[0], bb = Kp[1], c = Kp[2], d = Kp[3], e = Kp[4], f = Kp[5], g = Kp[6], hh = Kp[7], i = Kp[8];
-  double det = a * (e * i - f * hh) - bb * (d * i - f * g) + c * (d * hh - e * g);
-  double id = 1.0 / det;
-  o[0] = (float)((e * i - f * hh) * id);
-  o[1] = (float)((c * hh - bb * i) * id);
-  o[2] = (float)((bb * f - c * e) * id);
-  o[3] = (float)((f * g - d * i) * id);
-  o[4] = (float)((a * i - c * g) * id);
-  o[5] = (float)((c * d - a * f) * id);
-  o[6] = (float)((d * hh - e * g) * id);
-  o[7] = (float)((bb * g - a * hh) * id);
-  o[8] = (float)((a * e - bb * d) * id);
-  for (int k = 0; k < 9; ++k) o[9 + k] = Rp[k];
-  for (int k = 0; k < 3; ++k) o[18 + k] = tp[k];
-  // projection matrix P = K [R|t] (mvsnet.py:196-197).  torch.bmm evaluates this small batched product with rounded
-  // products and sequential additions (no FMA) -- unlike the large K^-1 p / R^T c / P X products, which are FMA chains
-  // in k order -- so contraction is switched off here: the sample coordinates then reproduce the reference's bit for bit
-  // (scripts/coord_order_probe.py)
-  for (int r = 0; r < 3; ++r)
-    for (int j = 0; j < 4; ++j) {
-      const float b0 = j < 3 ? Rp[0 * 3 + j] : tp[0], b1 = j < 3 ? Rp[1 * 3 + j] : tp[1], b2 = j < 3 ? Rp[2 * 3 + j] : tp[2];
-      o[24 + r * 4 + j] = v3d::add_rn(v3d::add_rn(v3d::mul_rn(Kp[r * 3 + 0], b0), v3d::mul_rn(Kp[r * 3 + 1], b1)),
-                                    v3d::mul_rn(Kp[r * 3 + 2], b2));
-    }
+  v3d::cam_block(K + img * 9, R + img * 9, t + img * 3, camp + img * kCamStride);
+}
+
+// Diagnostic twin of the warp kernels' projection (v3d_psv_sample_positions_f32): one thread per (edge, plane, pixel)
+// runs the SAME device functions (v3d::world_point / v3d::sample_position) and stores the un-normalised sample position,
+// so a test can compare the coordinates the kernels use with the reference's, bit for bit.
+__global__ __launch_bounds__(256) void psv_positions_kernel(PsvParams p, float* __restrict__ pos, float* __restrict__ world) {
+  const int P = p.h * p.w;
+  const long long n_vox = (long long)p.D * P;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int r = blockIdx.y;
+  if (i >= n_vox) return;
+  const int d = (int)(i / P), gp = (int)(i % P), gy = gp / p.w, gx = gp % p.w;
+  const float xf = v3d::psv_grid_coord(gx, p.w, p.W, p.x_step), yf = v3d::psv_grid_coord(gy, p.h, p.H, p.y_step);
+  const float z = v3d::psv_plane_depth(d, p.D, p.z_start, p.z_step, p.z_end);
+  float X, Y, Z;
+  v3d::world_point(p.camp + p.ref_img[r] * kCamStride, xf, yf, z, X, Y, Z);
+  if (world) {
+    world[((size_t)r * 3 + 0) * n_vox + i] = X;
+    world[((size_t)r * 3 + 1) * n_vox + i] = Y;
+    world[((size_t)r * 3 + 2) * n_vox + i] = Z;
+  }
+  const float Wm1 = (float)(p.W - 1), Hm1 = (float)(p.H - 1);
+  const float rWm1 = (float)(1.0 / (double)(p.W - 1)), rHm1 = (float)(1.0 / (double)(p.H - 1));
+  const float Wfm1 = (float)(p.Wf - 1), Hfm1 = (float)(p.Hf - 1);
+  for (int e = p.edge_ofs[r]; e < p.edge_ofs[r + 1]; ++e) {
+    float ix, iy;
+    v3d::sample_position(p.camp + p.edge_src[e] * kCamStride + 24, X, Y, Z, Wm1, rWm1, Hm1, rHm1, Wfm1, Hfm1, ix, iy);
+    pos[((size_t)e * n_vox + i) * 2] = ix;
+    pos[((size_t)e * n_vox + i) * 2 + 1] = iy;
+  }
 }
 
 struct TapInfo {      // one (pixel, plane, edge) sample, 32 bytes
@@ -168,15 +173,10 @@ struct TapInfo {      // one (pixel, plane, edge) sample, 32 bytes
 // sample instead of four.  CB = bytes per cell (4 C); first_cell = index of cell (-1, -1) of the source image.
 template <unsigned CB>
 __device__ __forceinline__ TapInfo make_taps(float ix, float iy, int Wf, int Hf, int first_cell) {
-  ix = fminf(fmaxf(ix, -1.f), (float)Wf);
-  iy = fminf(fmaxf(iy, -1.f), (float)Hf);
-  const float x0 = floorf(ix), y0 = floorf(iy);
-  const float x1 = x0 + 1.f, y1 = y0 + 1.f;
-  const float wx0 = x1 - ix, wx1 = ix - x0, wy0 = y1 - iy, wy1 = iy - y0;
+  const v3d::Footprint f = v3d::psv_footprint(ix, iy, Wf, Hf);      // psv_common.h: clamp, nw cell, weights
   TapInfo ti;
-  ti.w00 = v3d::mul_rn(wx0, wy0); ti.w01 = v3d::mul_rn(wx1, wy0);
-  ti.w10 = v3d::mul_rn(wx0, wy1); ti.w11 = v3d::mul_rn(wx1, wy1);
-  ti.b00 = (unsigned)(first_cell + ((int)y0 + 1) * (Wf + 2) + (int)x0 + 1) * CB;
+  ti.w00 = f.w00; ti.w01 = f.w01; ti.w10 = f.w10; ti.w11 = f.w11;
+  ti.b00 = (unsigned)(first_cell + ((int)f.y0 + 1) * (Wf + 2) + (int)f.x0 + 1) * CB;
   return ti;
 }
 
@@ -1055,37 +1055,6 @@ __global__ __launch_bounds__(SPLIT ? 64 : 256, V3D_PSV_WAVES) void psv_variance_
     }
   }      // chunk loop
 #undef V3D_PSV_BLEND
-}
-
-// Diagnostic twin of the warp kernels' projection (v3d_psv_sample_positions_f32): one thread per (edge, plane, pixel)
-// runs the SAME device functions (v3d::world_point / v3d::sample_position) and stores the un-normalised sample position,
-// so a test can compare the coordinates the kernels use with the reference's, bit for bit.
-__global__ __launch_bounds__(256) void psv_positions_kernel(PsvParams p, float* __restrict__ pos, float* __restrict__ world) {
-  const int P = p.h * p.w;
-  const long long n_vox = (long long)p.D * P;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  const int r = blockIdx.y;
-  if (i >= n_vox) return;
-  const int d = (int)(i / P), gp = (int)(i % P), gy = gp / p.w, gx = gp % p.w;
-  const float xf = (p.w > 1 && gx == p.w - 1) ? (float)(p.W - 1) : (float)((double)gx * p.x_step);
-  const float yf = (p.h > 1 && gy == p.h - 1) ? (float)(p.H - 1) : (float)((double)gy * p.y_step);
-  const float z = (d == p.D - 1 && p.D > 1) ? (float)p.z_end : (float)(p.z_start + (double)d * p.z_step);
-  float X, Y, Z;
-  v3d::world_point(p.camp + p.ref_img[r] * kCamStride, xf, yf, z, X, Y, Z);
-  if (world) {
-    world[((size_t)r * 3 + 0) * n_vox + i] = X;
-    world[((size_t)r * 3 + 1) * n_vox + i] = Y;
-    world[((size_t)r * 3 + 2) * n_vox + i] = Z;
-  }
-  const float Wm1 = (float)(p.W - 1), Hm1 = (float)(p.H - 1);
-  const float rWm1 = (float)(1.0 / (double)(p.W - 1)), rHm1 = (float)(1.0 / (double)(p.H - 1));
-  const float Wfm1 = (float)(p.Wf - 1), Hfm1 = (float)(p.Hf - 1);
-  for (int e = p.edge_ofs[r]; e < p.edge_ofs[r + 1]; ++e) {
-    float ix, iy;
-    v3d::sample_position(p.camp + p.edge_src[e] * kCamStride + 24, X, Y, Z, Wm1, rWm1, Hm1, rHm1, Wfm1, Hfm1, ix, iy);
-    pos[((size_t)e * n_vox + i) * 2] = ix;
-    pos[((size_t)e * n_vox + i) * 2 + 1] = iy;
-  }
 }
 
 }  // namespace

@@ -1,0 +1,130 @@
+"""Training of the cost-volume stage (stage 1): the pieces of ``mv3d/subnetworks/mvsnet.py:186-227`` and of the initial
+depth supervision (``mv3d/lightningmodel.py:57-63``) with a backward pass.
+
+Only one operation of stage 1 has no stock-torch route that is usable on the device: the fused warp + variance (rows
+A1-A4).  Its backward is ``csrc/psv_backward.hip`` behind ``v3d_psv_variance_backward_f32`` (include/v3d.h); like the forward
+it never materialises the warped volume, its square or the sampling grid -- the autograd node saves the features and the edge
+tables, nothing of size E * C * D * h * w.  Everything else -- CostRegNet's 3D convolutions, the soft-argmin, the masked MAE
+-- runs as stock differentiable torch ops over the parameters the inference modules already hold:
+
+  * ``PlaneSweepVariance`` / ``plane_sweep_variance``   the variance volume as an autograd function of the features;
+  * ``costregnet``                                       the regulariser of an existing ``mvsnet.CostRegNet``, functional;
+  * ``initial_depth_loss``                               variance -> regulariser -> soft-argmin -> masked MAE.
+
+Cameras, plane depths and edges are data (no gradient), as in the reference.  The gradient is summed with fp32 atomic adds:
+its last bits can differ from call to call.  Out of scope: stages 2 and 3, the native backbone, the split /
+channel-last variance formats, ``PL3DVNet.forward`` in training mode, an optimiser loop.  No CPU fallback.
+"""
+import torch
+import torch.nn.functional as F
+
+from . import _lib, mvsnet
+
+
+class PlaneSweepVariance(torch.autograd.Function):
+    """``mvsnet.plane_sweep_variance`` (the same kernel: the same bits) with a backward with respect to the features."""
+
+    @staticmethod
+    def forward(ctx, features_quarter, Kc, Rc, tc, ref_img, edge_ofs, edge_src, geom):
+        depth_start, depth_interval, n_planes, img_size, depth_img_size = geom
+        csr = mvsnet.EdgeCsr((ref_img.to(torch.int64), ref_img, edge_ofs, edge_src))
+        var = mvsnet.plane_sweep_variance(features_quarter, Rc, tc, Kc, None, depth_start, depth_interval, n_planes, img_size,
+                                          depth_img_size, csr=csr)
+        ctx.save_for_backward(features_quarter, Kc, Rc, tc, ref_img, edge_ofs, edge_src)
+        ctx.geom = geom
+        return var
+
+    @staticmethod
+    def backward(ctx, grad_var):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 8
+        features_quarter, Kc, Rc, tc, ref_img, edge_ofs, edge_src = ctx.saved_tensors
+        depth_start, depth_interval, n_planes, img_size, depth_img_size = ctx.geom
+        lib = _lib.load()
+        dev = features_quarter.device
+        n_img, C, Hf, Wf = features_quarter.shape
+        h, w = depth_img_size
+        feat_cl = features_quarter.detach().float().permute(0, 2, 3, 1).contiguous()
+        # a .sum() upstream hands autograd a stride-0 expanded tensor, a slice a non-contiguous one
+        grad_var = grad_var.float().contiguous()
+        assert grad_var.shape == (ref_img.shape[0], C, n_planes, h, w)
+        grad_cl = torch.empty((n_img, Hf, Wf, C), dtype=torch.float32, device=dev)      # zero-filled by the call
+        with torch.cuda.device(dev):
+            rc = lib.v3d_psv_variance_backward_f32(
+                _lib.ptr(feat_cl), _lib.ptr(Kc), _lib.ptr(Rc), _lib.ptr(tc), _lib.ptr(ref_img), _lib.ptr(edge_ofs),
+                _lib.ptr(edge_src), n_img, ref_img.shape[0], edge_src.shape[0], C, Hf, Wf, int(img_size[0]), int(img_size[1]),
+                float(depth_start), float(depth_interval), int(n_planes), int(h), int(w), _lib.ptr(grad_var),
+                _lib.ptr(grad_cl), _lib.stream_ptr(dev))
+        _lib.check(rc, 'v3d_psv_variance_backward_f32')
+        return (grad_cl.permute(0, 3, 1, 2).to(features_quarter.dtype),) + (None,) * 7
+
+
+def plane_sweep_variance(features_quarter, rotmats, tvecs, K, ref_src_edges, depth_start, depth_interval, n_planes, img_size,
+                         depth_img_size, csr=None, n_ref=None):
+    """Rows A1-A4 (mvsnet.py:186-216) as a differentiable function of ``features_quarter`` [n_img, C, Hf, Wf] (C in {16, 32}):
+    the variance volume [n_ref, C, D, h, w] of ``mvsnet.plane_sweep_variance``, bit for bit.  ``csr`` / ``n_ref`` as there."""
+    mvsnet._require_cuda(features_quarter, 'training.plane_sweep_variance')
+    dev = features_quarter.device
+    if csr is None:
+        csr = mvsnet.edges_to_csr(ref_src_edges.to(dev), n_ref=n_ref, n_img=features_quarter.shape[0])
+    _, ref_img, edge_ofs, edge_src = csr
+    Kc, Rc, tc = (x.detach().to(dev).contiguous().float() for x in (K, rotmats, tvecs))
+    geom = (float(depth_start), float(depth_interval), int(n_planes), (int(img_size[0]), int(img_size[1])),
+            (int(depth_img_size[0]), int(depth_img_size[1])))
+    return PlaneSweepVariance.apply(features_quarter, Kc, Rc, tc, ref_img, edge_ofs, edge_src, geom)
+
+
+def _conv_bn_relu(mod, x, bn_training):
+    if hasattr(mod, 'deconv'):
+        d = mod.deconv
+        y = F.conv_transpose3d(x, d.weight, None, stride=d.stride, padding=d.padding, output_padding=d.output_padding)
+    else:
+        y = F.conv3d(x, mod.conv.weight, None, stride=mod.conv.stride, padding=mod.conv.padding)
+    bn = mod.bn
+    y = F.batch_norm(y, bn.running_mean, bn.running_var, bn.weight, bn.bias, training=bn_training, momentum=bn.momentum,
+                     eps=bn.eps)
+    return F.relu(y)
+
+
+def costregnet(cnn_3d, x, bn_training=False):
+    """CostRegNet.forward (mvsnet.py:154-163) with stock differentiable torch ops over the parameters and buffers of an
+    existing ``mvsnet.CostRegNet`` (no second parameter set; its ``state_dict`` keys are untouched).  x [B, Cin, D, h, w] ->
+    [B, 1, D, h, w].  ``bn_training=False``: running statistics (the reference's ``freeze_batchnorm`` mode);
+    ``bn_training=True``: batch statistics, and the running buffers are updated."""
+    m = cnn_3d
+    conv0 = _conv_bn_relu(m.conv0, x, bn_training)
+    conv2 = _conv_bn_relu(m.conv2, _conv_bn_relu(m.conv1, conv0, bn_training), bn_training)
+    conv4 = _conv_bn_relu(m.conv4, _conv_bn_relu(m.conv3, conv2, bn_training), bn_training)
+    y = _conv_bn_relu(m.conv6, _conv_bn_relu(m.conv5, conv4, bn_training), bn_training)
+    y = conv4 + _conv_bn_relu(m.conv7, y, bn_training)
+    y = conv2 + _conv_bn_relu(m.conv8, y, bn_training)
+    y = conv0 + _conv_bn_relu(m.conv9, y, bn_training)
+    return F.conv3d(y, m.prob.weight, m.prob.bias, stride=1, padding=1)
+
+
+def masked_mae(depth_pred, depth_gt, depth_interval):
+    """The reference's ``MAELoss.forward`` (mv3d/loss.py:6-20) in differentiable torch: ground truth of another size reduced
+    with a nearest resize, pixels with ``gt != 0`` only, ``+ 1e-7`` in the denominator, in units of ``depth_interval``, mean
+    over the views."""
+    if depth_gt.shape != depth_pred.shape:
+        depth_gt = F.interpolate(depth_gt.unsqueeze(1), depth_pred.shape[-2:], mode='nearest').squeeze(1)
+    mask = (depth_gt != 0).to(depth_pred.dtype)
+    denom = mask.sum(dim=(1, 2)) + 1e-7
+    mae = (mask * (depth_pred - depth_gt).abs()).sum(dim=(1, 2))
+    return ((mae / depth_interval) / denom).mean()
+
+
+def initial_depth_loss(mvsnet_module, features_quarter, batch, depth_config, depth_gt, bn_training=False):
+    """Stage 1 with its supervision (mvsnet.py:186-227, lightningmodel.py:57-63) -> ``(loss, depth [n_ref, h, w])``.
+    ``mvsnet_module``: an ``mvsnet.MVSNet`` (its ``cnn_3d`` and ``img_size`` are used); ``features_quarter`` comes from the
+    caller's own differentiable backbone or is a leaf; ``depth_config``: ``depth_start``, ``depth_interval``, ``n_intervals``,
+    ``size``; ``depth_gt`` [n_ref, H, W].  The gradient of the loss reaches ``features_quarter`` and every parameter of
+    ``cnn_3d``."""
+    start, interval, n_planes = depth_config['depth_start'], depth_config['depth_interval'], depth_config['n_intervals']
+    var = plane_sweep_variance(features_quarter, batch.rotmats, batch.tvecs, batch.K, batch.ref_src_edges, start, interval,
+                               n_planes, mvsnet_module.img_size, depth_config['size'])
+    x_reg = costregnet(mvsnet_module.cnn_3d, var, bn_training=bn_training).squeeze(1)
+    prob = F.softmax(-x_reg, dim=1)
+    vals = mvsnet_module.depth_values(start, interval, n_planes, var.device).view(1, n_planes, 1, 1)
+    depth = torch.sum(vals * prob, dim=1)
+    return masked_mae(depth, depth_gt.to(depth.device), interval), depth

@@ -920,6 +920,30 @@ int v3d_register_colour_u8(const uint8_t* colour, int n, int Hc, int Wc, const f
                            void* stream);
 int v3d_lut_u16(const uint16_t* in, size_t n_elems, const uint16_t* lut, uint16_t* out, void* stream);
 
+/* Training, stage 1: backward of v3d_psv_variance_f32 with respect to the features (csrc/psv_backward.hip; the autograd of
+ * mvsnet.py:209-216).
+ * ABI version: STILL 9 (additive: a new symbol, no changed signature).
+ *   Per reference view with cnt edges, per channel and voxel: x_e = bilinear sample of source e (zeros padding: a tap outside
+ *   the image adds nothing and receives no gradient), avg = sum_e x_e / cnt, and with gV = grad_var:
+ *       g_e = gV * 2 * (x_e - avg) / cnt,     grad_feat[src_e, tap, c] += w_tap * g_e   for the four taps.
+ *   Cameras and plane depths are data: the features are the only differentiable input.  The sample positions and weights
+ *   are those of the forward kernels, bit for bit (the same device functions, csrc/psv_common.h).
+ *   feat_cl      [n_img, Hf, Wf, C]  the features CHANNEL-LAST (the forward takes [n_img, C, Hf, Wf]);  C in {16, 32}
+ *   grad_var     [n_ref, C, D, h, w]
+ *   grad_feat_cl [n_img, Hf, Wf, C]  out: zero-filled by the call itself, then accumulated -- the caller allocates it
+ *                                    uninitialised; an image that appears in no edge ends with exact zeros.
+ *   K, R, t, the edge CSR and the scalar geometry arguments are those of v3d_psv_variance_f32.
+ * No scratch memory: the call takes none, allocates nothing and never synchronises; asynchronous on `stream`.
+ * Contributions are summed with fp32 atomic adds whose arrival order is not fixed: the last bits of the result can differ
+ * between two calls with the same inputs (each element stays within the fp32 bound of its sum).
+ * Host-side errors: V3D_ERR_BAD_ARG (null pointer), V3D_ERR_UNSUPPORTED (C), V3D_ERR_BAD_SHAPE (a size that is not positive,
+ * Hf or Wf > 32759, (Hf + 2) (Wf + 2) >= 2^28 - 1, n_img Hf Wf C >= 2^31, more than 2^31 - 1 workgroups). */
+int v3d_psv_variance_backward_f32(const float* feat_cl, const float* K, const float* R, const float* t,
+                                  const int32_t* ref_img, const int32_t* edge_ofs, const int32_t* edge_src,
+                                  int n_img, int n_ref, int n_edges, int C, int Hf, int Wf, int H, int W,
+                                  double depth_start, double depth_interval, int D, int h, int w,
+                                  const float* grad_var, float* grad_feat_cl, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

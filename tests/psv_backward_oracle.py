@@ -10,6 +10,10 @@ scatter -- is float64.  For every element i of ``grad_feat`` [n_img, C, Hf, Wf]:
           a bound of the sum of the ABSOLUTE contributions that also holds under the cancellation in x_e - avg.
 
 ``variant`` selects deliberately wrong gradients (tests/test_psv_backward_oracle.py shows the acceptance bound rejects them).
+
+Two families of cases: ``CASES`` (``make_case``: at most 4 edges per reference, one depth segment) and ``CHUNK_CASES``
+(``make_chunk_case``: 8, 9 and 17 edges per reference and 33 planes -- the kernel keeps the tap records of ``CHUNK`` = 8 edges in
+LDS and walks ``SEGMENT`` = 16 planes per workgroup, so these cross both boundaries).  ``build(param)`` makes either.
 """
 import importlib
 
@@ -19,6 +23,19 @@ from oracle import pinned as pin
 
 U = 2.0 ** -24          # unit roundoff of fp32
 CASES = [(16, 'rotated'), (32, 'rotated'), (32, 'sliding')]      # (C, cameras) of make_case
+CHUNK = 8               # edges whose tap records the kernel keeps in LDS at a time (psv_backward.hip: kBMaxE)
+SEGMENT = 16            # depth planes per workgroup (kBDS)
+CHUNK_CASES = [('chunk', 16, 'rotated'), ('chunk', 16, 'dense'), ('chunk', 32, 'rotated'), ('chunk', 32, 'dense')]
+CHUNK_VARIANTS = ('avg_first_chunk', 'drop_later_chunks', 'stale_records', 'first_segment', 'tail_plane')
+
+
+def case_id(param):
+    return '-'.join(str(x) for x in param)
+
+
+def build(param):
+    """A member of CASES or CHUNK_CASES -> its case."""
+    return make_chunk_case(*param[1:]) if param[0] == 'chunk' else make_case(*param)
 
 
 def make_case(C, cameras='rotated', seed=3):
@@ -37,7 +54,61 @@ def make_case(C, cameras='rotated', seed=3):
     g = torch.Generator().manual_seed(seed + 100)
     gvar = torch.randn((3, C, 8) + plane_size, generator=g, dtype=torch.float32)
     return dict(feat=feat, rotmats=rot, tvecs=tv, K=K, edges=edges, depth=(0.5, 0.25, 8), img_size=img_size,
-                plane_size=plane_size, gvar=gvar)
+                plane_size=plane_size, gvar=gvar, unused=4)
+
+
+def make_chunk_case(C, cameras='dense', edge_counts=(8, 9, 17), D=33, plane_size=(5, 7), n_img=19, seed=10):
+    """Cases that cross the kernel's edge chunks (8 edges) and depth segments (16 planes): image 32 x 40, features 8 x 10,
+    plane grid 5 x 7 (35 pixels, no multiple of the 2 or 4 pixels of a wave), D = 33 planes 0.125 apart from 0.5 (three
+    segments, the last with one live plane), 19 images.  Reference r (image r) has ``edge_counts[r]`` edges -- 8, 9, 17: exactly
+    one chunk, 8 + 1, 8 + 8 + 1 -- whose sources are drawn without repetition from images 0 .. n_img - 2; the last image is in no
+    edge.  The edge list is shuffled, so the CSR order (references sorted, list order within a reference) is not the list order.
+    cameras='rotated': 45 degrees of yaw per view as in make_case (mirrored samples, most samples outside);
+    cameras='dense': 2 degrees per view, every edge has in-image taps on a good part of its samples, so every chunk carries
+    gradient (with make_cameras' default of 6 degrees most edges of the later chunks are wholly outside).
+    ``seed`` draws the features, the edges and gvar.  With 'rotated' a source sees its reference only when their yaws are at most
+    one step apart, so which edges land in the later chunks decides how much gradient those chunks carry: seed 10 puts in-image
+    edges there (seed 3, make_case's, leaves 'drop_later_chunks' visible on a third of the affected elements only; see
+    tests/test_psv_backward_oracle.py)."""
+    syn = importlib.import_module('3dvnet_amd.synthetic')
+    img_size, feat_size = (32, 40), (8, 10)
+    rot, tv, K = (syn.make_cameras(n_img, img_size, seed=5, yaw_step_deg=45.0) if cameras == 'rotated' else
+                  syn.make_cameras(n_img, img_size, seed=11, yaw_step_deg=2.0))
+    feat = syn.make_features(n_img, C, *feat_size, seed=seed) * 2 - 1
+    g = torch.Generator().manual_seed(seed + 200)
+    pairs = [(r, int(s)) for r, n in enumerate(edge_counts) for s in torch.randperm(n_img - 1, generator=g)[:n]]
+    edges = torch.tensor(pairs, dtype=torch.long)[torch.randperm(len(pairs), generator=g)].t().contiguous()
+    gvar = torch.randn((len(edge_counts), C, D) + tuple(plane_size), generator=g, dtype=torch.float32)
+    return dict(feat=feat, rotmats=rot, tvecs=tv, K=K, edges=edges, depth=(0.5, 0.125, D), img_size=img_size,
+                plane_size=tuple(plane_size), gvar=gvar, unused=n_img - 1)
+
+
+def make_strip_case(seed=3):
+    """The widest feature map the entry point accepts: one strip Hf = 2, Wf = 32759, C = 16, two images (8 MB), each the
+    reference of two edges (itself and the other), D = 2, plane grid 3 x 64, two views 2 degrees of yaw apart over an image of
+    8 x 1024 pixels: the samples spread over the whole width, so the tap records carry columns far above 8 and 14 bits."""
+    syn = importlib.import_module('3dvnet_amd.synthetic')
+    img_size, feat_size, plane_size = (8, 1024), (2, 32759), (3, 64)
+    rot, tv, K = syn.make_cameras(2, img_size, seed=11, yaw_step_deg=2.0)
+    feat = syn.make_features(2, 16, *feat_size, seed=seed) * 2 - 1
+    edges = torch.tensor([[0, 1, 1, 0], [0, 1, 0, 1]], dtype=torch.long)
+    g = torch.Generator().manual_seed(seed + 300)
+    gvar = torch.randn((2, 16, 2) + plane_size, generator=g, dtype=torch.float32)
+    return dict(feat=feat, rotmats=rot, tvecs=tv, K=K, edges=edges, depth=(0.5, 0.25, 2), img_size=img_size,
+                plane_size=plane_size, gvar=gvar, unused=None)
+
+
+def block_count(case):
+    """Workgroups of the backward launch, computed as the entry point does: n_ref * ceil(h w / (64 / C)) * ceil(D / 16)."""
+    C, P, D = case['feat'].shape[1], case['plane_size'][0] * case['plane_size'][1], case['depth'][2]
+    ppw = 64 // C
+    return len(torch.unique(case['edges'][0])) * ((P + ppw - 1) // ppw) * ((D + SEGMENT - 1) // SEGMENT)
+
+
+def tap_columns(case):
+    """Columns of all in-image taps of all samples, long [n]."""
+    Hf, Wf = case['feat'].shape[2:]
+    return torch.cat([idx[ok] % Wf for _, _, ix, iy in positions(case) for _, idx, ok in _taps(ix, iy, Hf, Wf)])
 
 
 def positions(case):
@@ -70,25 +141,44 @@ def _taps(ix, iy, Hf, Wf):
 
 
 def gradient(case, gvar=None, variant=None):
-    """-> dict(g64, N, M), each [n_img, C, Hf, Wf] float64.  ``gvar`` [n_ref, C, D, h, w] (default: the case's).
-    variant: None | 'no_avg' (the -avg term dropped) | 'global_cnt' (cnt = all edges of the batch) | 'swap_ne_sw'."""
+    """-> dict(g64, N, M), each [n_img, C, Hf, Wf] float64, and cnt_max, the largest edge count of a reference.  ``gvar``
+    [n_ref, C, D, h, w] (default: the case's).
+    variant: None | 'no_avg' (the -avg term dropped) | 'global_cnt' (cnt = all edges of the batch) | 'swap_ne_sw', and the bugs a
+    chunked kernel could have (chunk membership by CSR position k within the reference):
+      'avg_first_chunk'    avg is summed over positions 0 .. 7 only, then divided by the full cnt;
+      'drop_later_chunks'  edges at position 8 or higher scatter nothing;
+      'stale_records'      an edge at position k >= 8 samples (its own source image) and scatters with the taps -- weights, cells,
+                           validity -- of the edge at position k % 8;
+      'first_segment'      planes d >= 16 contribute nothing;
+      'tail_plane'         plane D - 1 contributes nothing."""
     feat = case['feat'].double()
     n_img, C, Hf, Wf = feat.shape
-    gv = (case['gvar'] if gvar is None else gvar).double().reshape(-1, C, case['depth'][2] * case['plane_size'][0] * case['plane_size'][1])
+    D, n_pix = case['depth'][2], case['plane_size'][0] * case['plane_size'][1]
+    gv = (case['gvar'] if gvar is None else gvar).double().reshape(-1, C, D, n_pix)
+    if variant in ('first_segment', 'tail_plane'):
+        gv = gv.clone()
+        gv[:, :, (SEGMENT if variant == 'first_segment' else D - 1):] = 0.0
+    gv = gv.reshape(-1, C, D * n_pix)
     flat, aflat = feat.reshape(n_img, C, Hf * Wf), feat.abs().reshape(n_img, C, Hf * Wf)
     g64, M = torch.zeros_like(flat), torch.zeros_like(flat)
     N = torch.zeros((n_img, Hf * Wf), dtype=torch.float64)
     pos = positions(case)
+    cnt_max = 0
     for r in sorted({p[0] for p in pos}):
         mine = [p for p in pos if p[0] == r]
+        cnt_max = max(cnt_max, len(mine))
         cnt = float(len(pos) if variant == 'global_cnt' else len(mine))
         taps = [_taps(ix, iy, Hf, Wf) for _, _, ix, iy in mine]
         if variant == 'swap_ne_sw':
             taps = [[tp[0], (tp[1][0], tp[2][1], tp[2][2]), (tp[2][0], tp[1][1], tp[1][2]), tp[3]] for tp in taps]
+        if variant == 'stale_records':
+            taps = [taps[k % CHUNK] if k >= CHUNK else tp for k, tp in enumerate(taps)]
         xs = [sum(w[None] * flat[src][:, idx] for w, idx, _ in tp) for (_, src, _, _), tp in zip(mine, taps)]
         As = [sum(w[None] * aflat[src][:, idx] for w, idx, _ in tp) for (_, src, _, _), tp in zip(mine, taps)]
-        avg, Aavg = sum(xs) / cnt, sum(As) / cnt
-        for (_, src, _, _), tp, x, A in zip(mine, taps, xs, As):
+        avg, Aavg = sum(xs[:CHUNK] if variant == 'avg_first_chunk' else xs) / cnt, sum(As) / cnt
+        for k, ((_, src, _, _), tp, x, A) in enumerate(zip(mine, taps, xs, As)):
+            if variant == 'drop_later_chunks' and k >= CHUNK:
+                continue
             ge = gv[r] * 2.0 * (x if variant == 'no_avg' else x - avg) / cnt
             me = gv[r].abs() * (2.0 / cnt) * (A + Aavg)
             for w, idx, ok in tp:
@@ -96,13 +186,32 @@ def gradient(case, gvar=None, variant=None):
                 M[src].index_add_(1, idx, w[None] * me)
                 N[src].index_add_(0, idx, ok.double())
     shape = (n_img, C, Hf, Wf)
-    return dict(g64=g64.reshape(shape), M=M.reshape(shape), N=N[:, None].expand(n_img, C, Hf * Wf).reshape(shape).clone())
+    return dict(g64=g64.reshape(shape), M=M.reshape(shape), N=N[:, None].expand(n_img, C, Hf * Wf).reshape(shape).clone(),
+                cnt_max=cnt_max)
+
+
+def affected_images(case, variant):
+    """bool [n_img]: the images whose gradient a CHUNK_VARIANTS bug can change -- for 'avg_first_chunk' the sources of the
+    references with more than one chunk, for 'drop_later_chunks' / 'stale_records' their sources at CSR position 8 or higher,
+    for the plane variants all sources."""
+    pos = positions(case)
+    mask = torch.zeros(case['feat'].shape[0], dtype=torch.bool)
+    for r in sorted({p[0] for p in pos}):
+        srcs = [p[1] for p in pos if p[0] == r]
+        if variant in ('first_segment', 'tail_plane'):
+            mask[srcs] = True
+        elif len(srcs) > CHUNK:
+            mask[srcs if variant == 'avg_first_chunk' else srcs[CHUNK:]] = True
+    return mask
 
 
 def bound(orc):
-    """The acceptance bound of the HIP gradient, per element: (N + 32) 2^-24 M -- N additions in any order, and at most 32
-    roundings per contribution (two 4-tap blends, a mean of at most 9 terms, the subtraction, three products)."""
-    return (orc['N'] + 32.0) * U * orc['M']
+    """The acceptance bound of the HIP gradient, per element: (N + c) 2^-24 M -- N additions in any order, and at most c
+    roundings per contribution, c = 32 + max(0, cnt_max - 9) with cnt_max the largest edge count of a reference in the batch.
+    The 32 are two 4-tap blends, a mean of at most 9 terms, the subtraction and three products.  A mean of cnt terms is cnt - 1
+    additions and a division, each one rounding relative to a partial sum that M's (A_e + mean_e A_e) bounds; the 32 hold 9 of
+    them, so every term past the ninth adds one: with 17 edges c = 40.  c = 32 for every case of at most 9 edges per reference."""
+    return (orc['N'] + 32.0 + max(0, orc['cnt_max'] - 9)) * U * orc['M']
 
 
 def violations(g, orc):

@@ -1,6 +1,9 @@
 """GPU: backward of the plane-sweep variance (csrc/psv_backward.hip, 3dvnet_amd/training.py) against the float64 oracle of
-tests/psv_backward_oracle.py, per element, within the worst-case fp32 bound (N + 32) 2^-24 M; the whole supervised stage 1
-against float64 autograd of the oracle chain.  No bit-identity of the gradient is asserted anywhere: its sums are fp32 atomics."""
+tests/psv_backward_oracle.py, per element, within the worst-case fp32 bound (N + c) 2^-24 M (c = 32 up to 9 edges per reference,
+one more per further edge: pbo.bound); the whole supervised stage 1 against float64 autograd of the oracle chain.  No bit-identity
+of the gradient is asserted anywhere: its sums are fp32 atomics.  The cases of pbo.CHUNK_CASES, the segment sweep and the limits
+reach what the three cases of pbo.CASES do not: more than the 8 edges whose tap records fit in LDS (pass 2 projects every chunk a
+second time), more than one 16-plane depth segment, dead planes in the last one, block counts that are no multiple of 8."""
 import types
 
 import pytest
@@ -29,34 +32,76 @@ def _inside(g, orc, what):
     bad, worst, worst_zero = pbo.violations(g, orc)
     print('%s: worst |g - g64| / bound = %.3f, outside: %d, worst error where the bound is 0: %g' % (what, worst, bad, worst_zero))
     assert not torch.isnan(g).any(), what
-    assert bad == 0, '%s: %d elements outside (N + 32) 2^-24 M, worst ratio %.3f' % (what, bad, worst)
+    assert bad == 0, '%s: %d elements outside the bound of pbo.bound, worst ratio %.3f' % (what, bad, worst)
 
 
-@pytest.fixture(scope='module', params=pbo.CASES, ids=lambda p: '%d-%s' % p)
-def run(request, cuda):
+_RUNS = {}
+
+
+def _run(param, cuda):
     """One case, its oracle (computed once, never modified) and the gradient of two consecutive backward calls."""
-    case = pbo.make_case(*request.param)
-    orc = pbo.gradient(case)
-    feat, var = _variance(case, cuda)
-    gv = case['gvar'].to(cuda)
-    g1 = torch.autograd.grad(var, feat, grad_outputs=gv, retain_graph=True)[0]
-    g2 = torch.autograd.grad(var, feat, grad_outputs=gv)[0]
-    return types.SimpleNamespace(case=case, orc=orc, var=var.detach(), g1=g1, g2=g2, dev=cuda)
+    if param not in _RUNS:
+        case = pbo.build(param)
+        orc = pbo.gradient(case)
+        feat, var = _variance(case, cuda)
+        gv = case['gvar'].to(cuda)
+        g1 = torch.autograd.grad(var, feat, grad_outputs=gv, retain_graph=True)[0]
+        g2 = torch.autograd.grad(var, feat, grad_outputs=gv)[0]
+        _RUNS[param] = types.SimpleNamespace(case=case, orc=orc, var=var.detach(), g1=g1, g2=g2, dev=cuda)
+    return _RUNS[param]
 
 
-def test_forward_is_the_inference_kernel(run):
+@pytest.fixture(scope='module', params=pbo.CASES, ids=pbo.case_id)
+def run(request, cuda):
+    """The cases of at most 4 edges and 8 planes (reference 0 has a single edge)."""
+    return _run(request.param, cuda)
+
+
+@pytest.fixture(scope='module', params=pbo.CASES + pbo.CHUNK_CASES, ids=pbo.case_id)
+def run_all(request, cuda):
+    """Those, and the cases of 8, 9 and 17 edges with three depth segments."""
+    return _run(request.param, cuda)
+
+
+def _backward_raw(c, dev, feat_cl, gvar, out):
+    """v3d_psv_variance_backward_f32 itself on the cameras, edges and geometry of case ``c`` -> its return code."""
+    lib_mod, mvs = v3d('_lib'), v3d('mvsnet')
+    n_img, Hf, Wf, C = feat_cl.shape
+    _, ref_img, edge_ofs, edge_src = mvs.edges_to_csr(c['edges'].to(dev))
+    K, R, t = (x.to(dev).contiguous() for x in (c['K'], c['rotmats'], c['tvecs']))
+    start, interval, D = c['depth']
+    assert feat_cl.is_contiguous() and gvar.is_contiguous() and out.is_contiguous() and out.numel() == feat_cl.numel()
+    assert gvar.shape == (ref_img.shape[0], C, D) + tuple(c['plane_size'])
+    return lib_mod.load().v3d_psv_variance_backward_f32(
+        feat_cl.data_ptr(), K.data_ptr(), R.data_ptr(), t.data_ptr(), ref_img.data_ptr(), edge_ofs.data_ptr(), edge_src.data_ptr(),
+        n_img, ref_img.shape[0], edge_src.shape[0], C, Hf, Wf, c['img_size'][0], c['img_size'][1], start, interval, D,
+        c['plane_size'][0], c['plane_size'][1], gvar.data_ptr(), out.data_ptr(), lib_mod.stream_ptr(dev))
+
+
+def _poisoned(shape, byte, dev):
+    n = 1
+    for k in shape:
+        n *= k
+    return torch.full((n * 4,), byte, dtype=torch.uint8, device=dev).view(torch.float32).view(shape)
+
+
+def test_forward_is_the_inference_kernel(run_all):
     """1. the Function's forward is mvsnet.plane_sweep_variance, bit for bit."""
+    run = run_all
     mvs, c = v3d('mvsnet'), run.case
     want = mvs.plane_sweep_variance(c['feat'].to(run.dev), c['rotmats'], c['tvecs'], c['K'], c['edges'].to(run.dev), *_geom(c))
     assert run.var.shape == want.shape and torch.equal(run.var, want)
 
 
-def test_gradient_within_the_fp32_bound(run):
+def test_gradient_within_the_fp32_bound(run_all, request):
     """2. + 5. every element of two consecutive calls; 3. the unused image stays exactly zero."""
+    run = run_all
     assert run.g1.shape == run.case['feat'].shape and run.g1.dtype == torch.float32
-    _inside(run.g1, run.orc, 'first call')
-    _inside(run.g2, run.orc, 'second call')
-    assert not run.g1[4].any() and not run.g2[4].any()
+    _inside(run.g1, run.orc, '%s first call' % request.node.callspec.id)
+    _inside(run.g2, run.orc, '%s second call' % request.node.callspec.id)
+    unused = run.case['unused']
+    assert unused not in run.case['edges'].flatten().tolist()
+    assert not run.g1[unused].any() and not run.g2[unused].any()
     assert float(run.g1.abs().max()) > 0
 
 
@@ -70,8 +115,9 @@ def test_one_edge_reference_contributes_exactly_zero(run):
 
 
 @pytest.mark.parametrize('byte', [0x00, 0xFF])
-def test_output_poison(run, byte):
+def test_output_poison(run_all, byte):
     """4. the entry point zero-fills its accumulation target itself: an output of 0x00 bytes and one of 0xFF bytes (NaN)."""
+    run = run_all
     lib_mod, mvs, c, dev = v3d('_lib'), v3d('mvsnet'), run.case, run.dev
     lib = lib_mod.load()
     feat_cl = c['feat'].to(dev).permute(0, 2, 3, 1).contiguous()
@@ -88,8 +134,9 @@ def test_output_poison(run, byte):
     _inside(out.permute(0, 3, 1, 2), run.orc, 'output pre-filled with 0x%02X' % byte)
 
 
-def test_stride0_and_sliced_grad_output(run):
+def test_stride0_and_sliced_grad_output(run_all):
     """6. loss = var.sum() hands the backward a stride-0 expanded gradient; a slice of a wider tensor a non-contiguous one."""
+    run = run_all
     feat, var = _variance(run.case, run.dev)
     var.sum().backward()
     _inside(feat.grad, pbo.gradient(run.case, gvar=torch.ones_like(run.case['gvar'])), 'stride-0 grad_output')
@@ -115,6 +162,98 @@ def test_no_gradient_wanted_launches_nothing(run):
         def saved_tensors(self):
             raise AssertionError('the backward read its saved tensors although no gradient is wanted')
     assert tr.PlaneSweepVariance.backward(Ctx(), torch.ones_like(var)) == (None,) * 8
+
+
+# ---- depth segments, feature dtype and layout, the entry point's limits ------------------------------------------------
+@pytest.mark.parametrize('D', [15, 16, 17, 32])
+def test_segment_boundaries(cuda, D):
+    """One reference of 9 edges (two chunks) at plane counts around the 16-plane segment: one segment with a dead plane, exactly
+    one, one plus a single live plane, exactly two.  Then with only the last segment's grad_output non-zero: the gradient of the
+    tail alone is inside the same bound and not all zero."""
+    case = pbo.make_chunk_case(32, 'dense', edge_counts=(9,), D=D)
+    feat, var = _variance(case, cuda)
+    assert var.shape[2] == D
+    g = torch.autograd.grad(var, feat, grad_outputs=case['gvar'].to(cuda), retain_graph=True)[0]
+    orc = pbo.gradient(case)
+    assert orc['cnt_max'] == 9
+    _inside(g, orc, 'D = %d' % D)
+    assert float(g.abs().max()) > 0 and not g[case['unused']].any()
+    tail = torch.zeros_like(case['gvar'])
+    d0 = (D - 1) // pbo.SEGMENT * pbo.SEGMENT
+    tail[:, :, d0:] = case['gvar'][:, :, d0:]
+    g = torch.autograd.grad(var, feat, grad_outputs=tail.to(cuda))[0]
+    _inside(g, pbo.gradient(case, gvar=tail), 'D = %d, planes %d .. %d only' % (D, d0, D - 1))
+    assert float(g.abs().max()) > 0
+
+
+def test_feature_layout_and_dtype(cuda):
+    """The wrapper's copies going in (.float().permute().contiguous()) and coming out (.to(features_quarter.dtype)): features in
+    channels_last, features that are a channel slice of a wider tensor, and bfloat16 features -- the oracle then takes the bf16
+    values promoted to float64, and the result may carry one more bf16 rounding: |g - g64| <= bound + 2^-8 |g64|."""
+    tr = v3d('training')
+    param = ('chunk', 32, 'dense')
+    case, orc = pbo.build(param), _run(param, cuda).orc
+    gv = case['gvar'].to(cuda)
+
+    def grad(feat):
+        feat.requires_grad_(True)
+        var = tr.plane_sweep_variance(feat, case['rotmats'], case['tvecs'], case['K'], case['edges'], *_geom(case))
+        return torch.autograd.grad(var, feat, grad_outputs=gv)[0]
+    cl = case['feat'].to(cuda).contiguous(memory_format=torch.channels_last)
+    assert not cl.is_contiguous()
+    _inside(grad(cl), orc, 'channels_last features')
+    wide = torch.randn((19, 40, 8, 10), generator=torch.Generator().manual_seed(4)).to(cuda)
+    wide[:, 4:36] = case['feat'].to(cuda)
+    sliced = wide[:, 4:36].detach()
+    assert not sliced.is_contiguous() and torch.equal(sliced, case['feat'].to(cuda))
+    _inside(grad(sliced), orc, 'features sliced out of 40 channels')
+    bf = case['feat'].to(cuda).bfloat16()
+    g = grad(bf)
+    assert g.dtype == torch.bfloat16 and g.shape == bf.shape
+    orc16 = pbo.gradient(dict(case, feat=bf.detach().float().cpu()))
+    err = (g.double().cpu() - orc16['g64']).abs()
+    allowed = pbo.bound(orc16) + 2.0 ** -8 * orc16['g64'].abs()
+    nz = allowed > 0
+    print('bfloat16 features: worst |g - g64| / (bound + 2^-8 |g64|) = %.3f, outside: %d'
+          % (float((err[nz] / allowed[nz]).max()), int((~(err <= allowed)).sum())))
+    assert not torch.isnan(g).any() and bool((err <= allowed).all()) and float(g.abs().max()) > 0
+    assert not g[case['unused']].any()
+
+
+def test_widest_feature_map_is_accepted(cuda):
+    """Wf = 32759, the largest width the packed 16-bit columns of the tap records are declared for: accepted, inside the bound,
+    with taps (counted by the oracle) whose columns need more than 8 and more than 14 bits."""
+    c = pbo.make_strip_case()
+    cols = pbo.tap_columns(c)
+    assert int((cols >= 256).sum()) >= 1000 and int((cols >= 16384).sum()) > 0
+    feat_cl = c['feat'].to(cuda).permute(0, 2, 3, 1).contiguous()
+    out = _poisoned(tuple(feat_cl.shape), 0xFF, cuda)
+    rc = _backward_raw(c, cuda, feat_cl, c['gvar'].to(cuda), out)
+    v3d('_lib').check(rc, 'v3d_psv_variance_backward_f32')
+    g = out.permute(0, 3, 1, 2)
+    _inside(g, pbo.gradient(c), 'Hf = 2, Wf = 32759')
+    assert float(g[..., 16384:].abs().max()) > 0
+
+
+@pytest.mark.parametrize('what', ['Wf=32760', 'C=8'])
+def test_limits_are_refused_and_the_output_untouched(cuda, what):
+    """One column more than the tap records can pack, and a channel count the kernel has no instance for: the documented error
+    code, and an output of 0xFF bytes keeps every byte.  All buffers have the declared size."""
+    codes = {name: rc for rc, name in v3d('_lib')._ERR_NAMES.items()}
+    c = pbo.make_strip_case()
+    if what == 'Wf=32760':
+        shape, want = (2, 2, 32760, 16), codes['V3D_ERR_BAD_SHAPE']
+        gvar = c['gvar'].to(cuda)
+    else:
+        c = pbo.make_case(16)
+        shape, want = (5, 8, 10, 8), codes['V3D_ERR_UNSUPPORTED']
+        gvar = c['gvar'][:, :8].contiguous().to(cuda)
+    feat_cl = torch.rand(shape, generator=torch.Generator().manual_seed(1)).to(cuda)
+    out = _poisoned(shape, 0xFF, cuda)
+    rc = _backward_raw(c, cuda, feat_cl, gvar, out)
+    torch.cuda.synchronize()
+    assert rc == want, (rc, want)
+    assert bool((out.view(torch.uint8) == 0xFF).all())
 
 
 # ---- 8. the whole supervised stage ------------------------------------------------------------------------------------

@@ -75,6 +75,112 @@ def test_bound_is_tight_and_rejects_wrong_gradients(case_orc):
     assert not pbo.gradient(case, gvar=only_ref0)['g64'].any()
 
 
+# ---- cases that cross the kernel's edge chunks (8 edges) and depth segments (16 planes) ----------------------------------
+@pytest.fixture(scope='module', params=pbo.CHUNK_CASES, ids=pbo.case_id)
+def chunk_orc(request):
+    case = pbo.build(request.param)
+    return case, pbo.gradient(case)
+
+
+def _segment_walk(case):
+    """Per edge in CSR order: (reference row, in-image tap count per depth segment [n_seg], footprint steps along the depth axis
+    inside a segment that stay in the cell, steps that move to another cell).  The footprint is the kernel's: the nw cell of the
+    position clamped to [-1, Wf] x [-1, Hf]."""
+    Hf, Wf = case['feat'].shape[2:]
+    D, n_pix = case['depth'][2], case['plane_size'][0] * case['plane_size'][1]
+    seg = torch.arange(D) // pbo.SEGMENT
+    same_seg = (seg[1:] == seg[:-1])[:, None]
+    out = []
+    for r, _, ix, iy in pbo.positions(case):
+        n_in = sum(ok.long() for _, _, ok in pbo._taps(ix, iy, Hf, Wf)).view(D, n_pix)
+        per_seg = torch.stack([n_in[seg == k].sum() for k in range(int(seg[-1]) + 1)])
+        x0 = torch.floor(torch.nan_to_num(ix, nan=-1.0).clamp(-1, Wf)).view(D, n_pix)
+        y0 = torch.floor(torch.nan_to_num(iy, nan=-1.0).clamp(-1, Hf)).view(D, n_pix)
+        moved = (x0[1:] != x0[:-1]) | (y0[1:] != y0[:-1])
+        out.append((r, per_seg, int((~moved & same_seg).sum()), int((moved & same_seg).sum())))
+    return out
+
+
+def test_chunk_inputs_cross_the_boundaries():
+    """8, 9 and 17 edges (one chunk, 8 + 1, 8 + 8 + 1) in shuffled list order, an unused image, three depth segments with one
+    live plane in the last, block counts that are no multiple of the 8 XCDs; with the 'dense' cameras every chunk of the
+    multi-chunk references holds an edge with in-image taps in every depth segment, and every edge's footprint both stays in its
+    cell and moves to another along the depth axis (the register-resident tap sums see reuse and flush)."""
+    for param in pbo.CHUNK_CASES:
+        case = pbo.build(param)
+        edges = case['edges']
+        assert torch.bincount(edges[0]).tolist() == [8, 9, 17]
+        assert case['unused'] == 18 and 18 not in edges.flatten().tolist() and case['feat'].shape[0] == 19
+        assert edges[0].tolist() != sorted(edges[0].tolist())
+        for ref in range(3):                                  # sources without repetition
+            srcs = edges[1][edges[0] == ref].tolist()
+            assert len(set(srcs)) == len(srcs)
+        D = case['depth'][2]
+        assert D == 33 and (D + pbo.SEGMENT - 1) // pbo.SEGMENT == 3 and D % pbo.SEGMENT == 1
+        blocks = pbo.block_count(case)
+        assert blocks == {16: 81, 32: 162}[param[1]] and blocks % 8 != 0
+        walk = _segment_walk(case)
+        stays, moves = sum(w[2] for w in walk), sum(w[3] for w in walk)
+        print('%s: %d blocks, footprint steps inside a segment: %d stay, %d move' % (pbo.case_id(param), blocks, stays, moves))
+        assert stays > 0 and moves > 0
+        if param[2] != 'dense':
+            continue
+        for r in (1, 2):
+            mine = [w for w in walk if w[0] == r]
+            for k in range(0, len(mine), pbo.CHUNK):
+                assert any(bool((w[1] > 0).all()) for w in mine[k:k + pbo.CHUNK]), (r, k)
+        assert all(w[2] > 0 and w[3] > 0 for w in walk)
+        print('   moves per edge: %d .. %d' % (min(w[3] for w in walk), max(w[3] for w in walk)))
+
+
+def test_chunk_oracle_matches_autograd(chunk_orc):
+    """test_oracle_matches_autograd on the chunk cases, the same threshold."""
+    test_oracle_matches_autograd(chunk_orc)
+
+
+def test_chunk_bound_is_tight_and_rejects_wrong_gradients(chunk_orc):
+    """The widened bound (N + 32 + max(0, cnt_max - 9)) 2^-24 M, cnt_max = 17: at most 1e-3 max|g64| on at least 99 % of the
+    elements; the three old wrong gradients violate it on at least half of the non-zero elements; each bug a chunked kernel could
+    have (pbo.CHUNK_VARIANTS) violates it on at least half of the non-zero elements of the images it can affect.
+    Inputs: the case seed is 10, not make_case's 3.  With seed 3 the 'rotated' cases (45 degrees of yaw per view, a source sees
+    its reference only from at most one step away) drew later-chunk edges that are mostly wholly outside, and the chunk variants
+    measured avg_first_chunk 50.6 %, drop_later_chunks 33.7 %, stale_records 68.1 % (C = 16; C = 32: 50.8 / 33.8 / 68.2).  Measured
+    with seed 10 (rotated / dense, C = 16 and 32 alike to a few tenths): avg_first_chunk 89.2 % / 99.6 %, drop_later_chunks 79.1 % /
+    100 %, stale_records 100 % / 100 %, first_segment 98.6 % / 100 %, tail_plane 95.5 % / 99.9 %; no_avg, global_cnt and
+    swap_ne_sw 99.2 - 100 %."""
+    case, orc = chunk_orc
+    assert orc['cnt_max'] == 17
+    b, scale = pbo.bound(orc), float(orc['g64'].abs().max())
+    tight = float((b <= 1e-3 * scale).double().mean())
+    print('bound <= 1e-3 max|g64| on %.2f %% of the elements; max bound / max|g64| = %.3g' % (100 * tight, float(b.max()) / scale))
+    assert tight >= 0.99
+    nonzero = orc['g64'] != 0
+    assert int(nonzero.sum()) > 1000
+    for variant in ('no_avg', 'global_cnt', 'swap_ne_sw') + pbo.CHUNK_VARIANTS:
+        wrong = pbo.gradient(case, variant=variant)['g64']
+        images = pbo.affected_images(case, variant) if variant in pbo.CHUNK_VARIANTS else torch.ones(19, dtype=torch.bool)
+        where = nonzero & images[:, None, None, None]
+        assert int(where.sum()) > 1000, variant
+        bad = ((wrong - orc['g64']).abs() > b) & where
+        frac = float(bad.sum()) / float(where.sum())
+        print('%s: outside the bound on %.1f %% of the %d non-zero elements of the %d images it can affect'
+              % (variant, 100 * frac, int(where.sum()), int(images.sum())))
+        assert frac >= 0.5, variant
+    assert pbo.violations(orc['g64'], orc)[0] == 0
+    assert not orc['g64'][case['unused']].any() and not orc['N'][case['unused']].any()
+
+
+def test_strip_case_exercises_the_packed_columns():
+    """The widest accepted feature map (Wf = 32759): the oracle counts the in-image taps whose column needs more than 8 and more
+    than 14 bits of the tap record's packed 16-bit columns."""
+    case = pbo.make_strip_case()
+    assert tuple(case['feat'].shape) == (2, 16, 2, 32759)
+    cols = pbo.tap_columns(case)
+    print('in-image taps: %d, column >= 256: %d, column >= 16384: %d, largest column %d'
+          % (cols.numel(), int((cols >= 256).sum()), int((cols >= 16384).sum()), int(cols.max())))
+    assert int((cols >= 256).sum()) >= 1000 and int((cols >= 16384).sum()) > 0
+
+
 def test_training_module_on_the_cpu():
     """(c) the module imports, the autograd function refuses CPU tensors, and the functional regulariser with running
     statistics equals oracle.costvolume.costregnet."""

@@ -87,7 +87,7 @@ def build(force=False, verbose=False, strict=False):
             isa_check.check_no_scratch(os.path.join(objdir, 'meshrender.o'), 'mesh_render_kernel', strict=strict)
             # plane-sweep warp: the window kernel walks the depth axis at the register limit of 4 waves per SIMD; what it keeps
             # across the walk must stay in registers
-            isa_check.check_no_scratch(os.path.join(objdir, 'psv_variance.o'), 'psv_variance_window_kernel', strict=strict)
+            isa_check.check_no_scratch(os.path.join(objdir, 'psv_window.o'), 'psv_variance_window_kernel', strict=strict)
             # its backward: the 16 plane means, the 16 scaled gradients and the four tap sums of a lane stay in registers
             isa_check.check_no_scratch(os.path.join(objdir, 'psv_backward.o'), 'psv_variance_backward_kernel', strict=strict)
             # confidence: the running maximum, the denominator and the two plane indices of a pixel stay in registers

@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void backproject_variance_kernel(BpParams p) {
       int src = p.edge_src[e_begin + ec + e];
       const float* Kp = p.K + src * 9; const float* Rp = p.R + src * 9; const float* tp = p.t + src * 3;
       float v;
-      // small batched product of torch.bmm: rounded products, sequential additions, no FMA (see psv_variance.hip)
+      // small batched product of torch.bmm: rounded products, sequential additions, no FMA (see psv_common.h, cam_block)
       const float b0 = j < 3 ? Rp[0 * 3 + j] : tp[0], b1 = j < 3 ? Rp[1 * 3 + j] : tp[1], b2 = j < 3 ? Rp[2 * 3 + j] : tp[2];
       v = v3d::add_rn(v3d::add_rn(v3d::mul_rn(Kp[i * 3 + 0], b0), v3d::mul_rn(Kp[i * 3 + 1], b1)), v3d::mul_rn(Kp[i * 3 + 2], b2));
       s_P[e][ij] = v;

@@ -1,4 +1,4 @@
-// Backward of the fused plane-sweep warp + variance (rows A1-A4, psv_variance.hip) with respect to the features
+// Backward of the fused plane-sweep warp + variance (rows A1-A4; psv_variance.hip is the map of the forward) with respect to the features
 // (v3d_psv_variance_backward_f32, include/v3d.h).  Reference semantics: the autograd of mvsnet.py:209-216.
 //
 // Per reference view r with cnt edges, per channel and voxel:  x_e = bilinear sample of source e (zeros padding),
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(64) void psv_variance_backward_kernel(PsvBwdParams 
   const int lane = threadIdx.x;
   const int c = lane % C, px = lane / C;
   int b = v3d::xcd_contiguous_block();
-  const int dseg = b % p.n_dseg; b /= p.n_dseg;         // depth segments fastest (see psv_variance.hip)
+  const int dseg = b % p.n_dseg; b /= p.n_dseg;         // depth segments fastest (see psv_fallback.hip, the reuse kernel)
   const int ptile = b % p.n_ptile;
   const int r = b / p.n_ptile;
   const int P = p.h * p.w;

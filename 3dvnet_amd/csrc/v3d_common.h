@@ -230,7 +230,7 @@ __device__ __forceinline__ void sample_position(const float* Pm, float X, float 
   iy = mul_rn(add_rn(gy, 1.f), mul_rn(0.5f, Hfm1));
 }
 
-// [n_img, C, HW] -> [n_img, HW, C] (C in {16, 32}); defined in psv_variance.hip
+// [n_img, C, HW] -> [n_img, HW, C] (C in {16, 32}); defined in psv_prepare.hip
 int transpose_channel_last(const float* feat, float* featT, int n_img, int C, int HW, hipStream_t s);
 
 }  // namespace v3d

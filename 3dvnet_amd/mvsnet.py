@@ -40,10 +40,22 @@ class _Workspace:
         return (_Workspace, ())
 
 
-def _psv_kernel_option():
-    v = ctypes.c_int(0)
-    _lib.check(_lib.load().v3d_get_option(b'psv_kernel', ctypes.byref(v)), 'v3d_get_option')
-    return v.value
+# entry points by layout of the variance volume (a key of _lib.LAYOUT): (plane-sweep variance, regulariser chain)
+_LAYOUT_ENTRY = {'reference': ('v3d_psv_variance_f32', 'v3d_costreg_depth_f32'),
+                 'split': ('v3d_psv_variance_split', 'v3d_costreg_depth_split'),
+                 'cl8': ('v3d_psv_variance_cl8', 'v3d_costreg_depth_cl8')}
+
+
+def _layout(split, cl8):
+    return 'cl8' if cl8 else 'split' if split else 'reference'
+
+
+def _psv_kernel_choice(feat_shape):
+    """The warp kernel the library runs for feature maps [n_img, C, Hf, Wf] (include/v3d.h): 0 window, 1 reuse, 2 gather."""
+    choice = _lib.load().v3d_psv_kernel_choice(*(int(v) for v in feat_shape))
+    if choice < 0:
+        _lib.check(choice, 'v3d_psv_kernel_choice')
+    return choice
 
 
 def module_state_key(module):
@@ -209,21 +221,21 @@ class CostRegNet(nn.Module):
         depth_vals = depth_vals.to(device=x.device, dtype=torch.float32).contiguous()
         if return_prob:
             prob = torch.empty((B, h, w), dtype=torch.float32, device=x.device)
-            rc = lib.v3d_costreg_depth_prob(handle, _lib.ptr(x), _lib.LAYOUT['cl8' if cl8 else 'split' if split else 'reference'],
+            rc = lib.v3d_costreg_depth_prob(handle, _lib.ptr(x), _lib.LAYOUT[_layout(split, cl8)],
                                             _lib.precision_code(precision), _lib.ptr(depth_vals), float(depth_start),
                                             float(depth_interval), B, D, h, w, _lib.ptr(depth), _lib.ptr(reg), _lib.ptr(prob),
                                             _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device))
             _lib.check(rc, 'v3d_costreg_depth_prob')
             return (depth, reg, prob) if return_reg else (depth, prob)
+        entry = _LAYOUT_ENTRY[_layout(split, cl8)][1]
         if split or cl8:
-            fn = lib.v3d_costreg_depth_cl8 if cl8 else lib.v3d_costreg_depth_split
-            rc = fn(handle, _lib.ptr(x), _lib.ptr(depth_vals), B, D, h, w, _lib.ptr(depth),
-                    _lib.ptr(reg), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device))
+            rc = getattr(lib, entry)(handle, _lib.ptr(x), _lib.ptr(depth_vals), B, D, h, w, _lib.ptr(depth),
+                                     _lib.ptr(reg), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device))
         else:
             rc = lib.v3d_costreg_depth_f32(handle, _lib.ptr(x), _lib.ptr(depth_vals), B, D, h, w, _lib.ptr(depth),
                                            _lib.ptr(reg), _lib.precision_code(precision), _lib.ptr(ws), ws.numel(),
                                            _lib.stream_ptr(x.device))
-        _lib.check(rc, 'v3d_costreg_depth_cl8' if cl8 else 'v3d_costreg_depth_split' if split else 'v3d_costreg_depth_f32')
+        _lib.check(rc, entry)
         return (depth, reg) if return_reg else depth
 
     def run_layer(self, layer, x, skip=None, split=False, precision='split_bf16'):
@@ -355,12 +367,13 @@ def plane_sweep_variance(features_quarter, rotmats, tvecs, K, ref_src_edges, dep
     nbytes = lib.v3d_psv_workspace_bytes(n_img, C, Hf, Wf)
     ws = (workspace or _Workspace()).get('psv', nbytes, dev)
     Kc, Rc, tc = (x.to(dev).contiguous().float() for x in (K, rotmats, tvecs))
-    fn = lib.v3d_psv_variance_cl8 if cl8 else lib.v3d_psv_variance_split if split else lib.v3d_psv_variance_f32
+    entry = _LAYOUT_ENTRY[_layout(split, cl8)][0]
+    fn = getattr(lib, entry)
     rc = fn(_lib.ptr(feat), _lib.ptr(Kc), _lib.ptr(Rc), _lib.ptr(tc), _lib.ptr(ref_img),
             _lib.ptr(edge_ofs), _lib.ptr(edge_src), n_img, n_ref, n_edges, C, Hf, Wf, int(img_size[0]),
             int(img_size[1]), float(depth_start), float(depth_interval), int(n_planes), int(h), int(w),
             _lib.ptr(var), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-    _lib.check(rc, 'v3d_psv_variance_cl8' if cl8 else 'v3d_psv_variance_split' if split else 'v3d_psv_variance_f32')
+    _lib.check(rc, entry)
     return Cl8Variance(var, var.shape) if cl8 else SplitVariance(var, var.shape) if split else var
 
 
@@ -379,7 +392,7 @@ def plane_sweep_sample_positions(rotmats, tvecs, K, ref_src_edges, depth_start, 
     n_img = Kc.shape[0]
     pos = torch.empty((n_edges, n_vox, 2), dtype=torch.float32, device=dev)
     world = torch.empty((n_ref, 3, n_vox), dtype=torch.float32, device=dev)
-    ws = torch.empty(n_img * 36 * 4 + 256, dtype=torch.uint8, device=dev)
+    ws = torch.empty(n_img * 36 * 4 + 256, dtype=torch.uint8, device=dev)      # n_img camera blocks of kCamStride = 36 floats (csrc/psv_common.h)
     rc = lib.v3d_psv_sample_positions_f32(_lib.ptr(Kc), _lib.ptr(Rc), _lib.ptr(tc), _lib.ptr(ref_img), _lib.ptr(edge_ofs),
                                           _lib.ptr(edge_src), n_img, n_ref, n_edges, int(feat_size[0]), int(feat_size[1]),
                                           int(img_size[0]), int(img_size[1]), float(depth_start), float(depth_interval),
@@ -434,10 +447,10 @@ class MVSNet(nn.Module):
         precision = precision or self.cnn_3d.precision
         split = not return_intermediates and features_quarter.shape[1] == 32 and precision == 'split_bf16'
         # exact fp32: the volume in the channel-last fp32 layout conv0's depth march streams (same numbers as the reference layout).
-        # Only the window kernel writes it: developer runs of the reuse / gather kernels (v3d_set_option "psv_kernel") and feature
-        # stacks of 2 GB or more (which take the reuse kernel) keep the reference layout and the per-layer conv0.
+        # Only the window kernel writes it (v3d_psv_kernel_choice = 0): developer runs of the reuse / gather kernels and feature
+        # stacks whose bordered copy has 2 GB or more (which take the reuse kernel) keep the reference layout and the per-layer conv0.
         cl8 = (not return_intermediates and features_quarter.shape[1] == 32 and precision == 'fp32'
-               and features_quarter.numel() * 4 < 2 ** 31 and _psv_kernel_option() == 0)
+               and _psv_kernel_choice(features_quarter.shape) == 0)
         if csr is None:
             # kept on the module: `check_edges()` reads the device builder's status word (a wrong n_ref gives an EMPTY edge
             # table, i.e. a zero variance volume and a plausible-looking depth, not an exception)

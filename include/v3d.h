@@ -944,6 +944,12 @@ int v3d_psv_variance_backward_f32(const float* feat_cl, const float* K, const fl
                                   double depth_start, double depth_interval, int D, int h, int w,
                                   const float* grad_var, float* grad_feat_cl, void* stream);
 
+/* Which warp kernel v3d_psv_variance_* runs for feature maps [n_img, C, Hf, Wf]: 0 the window kernel, 1 the reuse kernel (bordered
+ * channel-last copy of 2 GB and more, or the developer option "psv_kernel" = 1), 2 the gather kernel (C = 16, or "psv_kernel" = 2);
+ * negative: C or a size the variance rejects.  Only choice 0 writes the layout of v3d_psv_variance_cl8.
+ * ABI version: STILL 9 (additive: a new symbol, no changed signature). */
+int v3d_psv_kernel_choice(int n_img, int C, int Hf, int Wf);
+
 #ifdef __cplusplus
 }
 #endif

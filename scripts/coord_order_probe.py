@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Developer probe (CPU only): which fp32 evaluation order reproduces torch's CPU arithmetic -- i.e. the oracle's and the
 reference's -- for the plane-sweep sample coordinates and the bilinear taps?  Candidate orders are emulated in numpy (FMA via
-float64) and compared BITWISE with the torch ops.  Findings (torch 2.10 CPU, MKL), which psv_variance.hip / backproject.hip follow:
+float64) and compared BITWISE with the torch ops.  Findings (torch 2.10 CPU, MKL), which psv_common.h / backproject.hip follow:
   * the large batched products K^-1 p, R^T c and P [X;1] (MKL sgemm):      FMA chain in k order, first term a plain product
   * the small batched product P = K [R|t] (bmm's naive kernel, < 400 MACs): rounded products, sequential additions, NO FMA
   * tensor / python_float:                                                 true division

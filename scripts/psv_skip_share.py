@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""How much of the window warp kernel's work the pass skip (csrc/psv_variance.hip, developer option psv_skip) can leave out at
+"""How much of the window warp kernel's work the pass skip (csrc/psv_window.hip, developer option psv_skip) can leave out at
 a given shape: the share of samples that fall wholly beside their source image, of (8 pixels, plane, edge) steps made of such
 samples only, and of (8 pixels, 8 planes, edge) passes made of such samples only -- the passes the kernel skips.  CPU only.
 
@@ -17,7 +17,7 @@ import sys
 
 import numpy as np
 
-PIX, PLANES = 8, 8       # kRPix, kRDB of csrc/psv_variance.hip
+PIX, PLANES = 8, 8       # kRPix, kRDB of csrc/psv_kernels.h
 
 
 def sample_positions(rotmats, tvecs, K, edges, depth_start, depth_interval, n_planes, img_size, feat_size, plane_size):

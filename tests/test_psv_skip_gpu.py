@@ -1,4 +1,4 @@
-"""Pass skip of the window warp kernel (csrc/psv_variance.hip; developer option psv_skip, default 1): a pass -- one edge, 8 planes,
+"""Pass skip of the window warp kernel (csrc/psv_window.hip; developer option psv_skip, default 1): a pass -- one edge, 8 planes,
 8 pixels -- whose 64 samples all fall beside the source image adds exactly zero to the sums and is left out.  Every variant must
 give the bits of psv_skip = 0, the kernel that never skips, and the reuse kernel (which has no skip) must give them too.
 

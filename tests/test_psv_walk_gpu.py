@@ -1,4 +1,4 @@
-"""Depth walk of the window warp kernel (csrc/psv_variance.hip): a wave keeps its 8 pixels for W consecutive 8-plane chunks
+"""Depth walk of the window warp kernel (csrc/psv_window.hip): a wave keeps its 8 pixels for W consecutive 8-plane chunks
 (developer option psv_walk; 0 = W chosen from the shape).  Every W must give the bits of W = 1 (the kernel variant without the
 walk) and of the reuse kernel.  At these small shapes the shape rule itself gives W = 1, so 'auto' repeats that variant here: the
 rule is checked on the host by tests/test_psv_walk.py, and an auto W > 1 runs in the full-size tests of

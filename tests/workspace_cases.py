@@ -1087,7 +1087,7 @@ CASES.append(Case(
     sections=lambda lib, i: {'psv': lib.v3d_psv_workspace_bytes(i['n_img'], 32, 16, 20)},
     groups=lambda i: [('warp kernel: tiles of 8 pixels, per view and chunk of 8 planes', i['h'] * i['w'], 8,
                        np.unique(i['edges'][0]).size * -(-i['D'] // 8))],
-    constants=(('kRPix = 8', 'psv_variance.hip:389'), ('8 planes x 8 pixels = 64 lanes', 'psv_variance.hip:663')), rule_on='big'))
+    constants=(('kRPix = 8', 'psv_kernels.h:75'), ('8 planes x 8 pixels = 64 lanes', 'psv_window.hip:52')), rule_on='big'))
 
 
 _NETS = {}

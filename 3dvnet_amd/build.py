@@ -90,6 +90,9 @@ def build(force=False, verbose=False, strict=False):
             isa_check.check_no_scratch(os.path.join(objdir, 'psv_window.o'), 'psv_variance_window_kernel', strict=strict)
             # its backward: the 16 plane means, the 16 scaled gradients and the four tap sums of a lane stay in registers
             isa_check.check_no_scratch(os.path.join(objdir, 'psv_backward.o'), 'psv_variance_backward_kernel', strict=strict)
+            # the back-projected variance's backward: the same state per hypothesis segment; the depth kernel's chains
+            isa_check.check_no_scratch(os.path.join(objdir, 'backproject_backward.o'), 'backproject_[a-z]*_backward_kernel',
+                                       strict=strict)
             # confidence: the running maximum, the denominator and the two plane indices of a pixel stay in registers
             isa_check.check_no_scratch(os.path.join(objdir, 'confidence.o'), 'soft_argmin_prob_kernel', strict=strict)
             isa_check.check_no_scratch(os.path.join(objdir, 'confidence.o'), 'prob_gather_kernel', strict=strict)

@@ -1,5 +1,5 @@
-"""Training of the cost-volume stage (stage 1): the pieces of ``mv3d/subnetworks/mvsnet.py:186-227`` and of the initial
-depth supervision (``mv3d/lightningmodel.py:57-63``) with a backward pass.
+"""Training of the cost-volume stage (stage 1) and of the entry of stage 2: the pieces of ``mv3d/subnetworks/mvsnet.py:186-227``,
+of the initial depth supervision (``mv3d/lightningmodel.py:57-63``) and of the back-projected variance with a backward pass.
 
 Only one operation of stage 1 has no stock-torch route that is usable on the device: the fused warp + variance (rows
 A1-A4).  Its backward is ``csrc/psv_backward.hip`` behind ``v3d_psv_variance_backward_f32`` (include/v3d.h); like the forward
@@ -11,14 +11,25 @@ tables, nothing of size E * C * D * h * w.  Everything else -- CostRegNet's 3D c
   * ``costregnet``                                       the regulariser of an existing ``mvsnet.CostRegNet``, functional;
   * ``initial_depth_loss``                               variance -> regulariser -> soft-argmin -> masked MAE.
 
-Cameras, plane depths and edges are data (no gradient), as in the reference.  The gradient is summed with fp32 atomic adds:
-its last bits can differ from call to call.  Out of scope: stages 2 and 3, the native backbone, the split /
-channel-last variance formats, ``PL3DVNet.forward`` in training mode, an optimiser loop.  No CPU fallback.
+The entry of stage 2 is the back-projected variance (rows B1-B2 / C1, ``mv3d/lightningmodel.py:132-174, 187-235``).  Its backward
+is ``csrc/backproject_backward.hip`` behind ``v3d_backproject_variance_backward_f32``: the only place where a stage-2 loss reaches
+the image features and the stage-1 depth.  Its node saves the features, the depth map, the cameras and the edge tables:
+
+  * ``BackprojectVariance`` / ``backproject_variance``   ``(pts, var)``: ``var`` -> features; with ``n == 0`` ``pts`` -> depth;
+  * ``feature_rich_pointcloud``                          the differentiable twin of ``construct_feature_rich_pointcloud``;
+  * ``pointflow_hypotheses``                             the hypothesis points and features of ``run_pointflow``.
+
+Cameras, plane depths, offsets and edges are data (no gradient), as in the reference, which also builds every sampling grid under
+``no_grad``.  The feature gradients are summed with fp32 atomic adds: their last bits can differ from call to call (DESIGN.md
+4.1b, 4.1c).  Out of scope: the rest of stage 2 (PointNet, the sparse U-Net, the trilinear interpolation, the decoder), stage 3,
+the native backbone, the split / channel-last variance formats, ``PL3DVNet.forward`` in training mode, an optimiser loop
+(DESIGN.md 6).  No CPU fallback.
 """
 import torch
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
-from . import _lib, mvsnet
+from . import _lib, lightningmodel, mvsnet
 
 
 class PlaneSweepVariance(torch.autograd.Function):
@@ -72,6 +83,102 @@ def plane_sweep_variance(features_quarter, rotmats, tvecs, K, ref_src_edges, dep
     geom = (float(depth_start), float(depth_interval), int(n_planes), (int(img_size[0]), int(img_size[1])),
             (int(depth_img_size[0]), int(depth_img_size[1])))
     return PlaneSweepVariance.apply(features_quarter, Kc, Rc, tc, ref_img, edge_ofs, edge_src, geom)
+
+
+class BackprojectVariance(torch.autograd.Function):
+    """``lightningmodel.backproject_variance`` (the same kernel: the same bits) -> ``(pts, var)`` with the two gradients the
+    reference has (lightningmodel.py:132-174, 187-235; the grid is built under ``no_grad`` there): ``var`` -> features, and, for
+    ``n == 0`` only, ``pts`` -> depth.  With ``n > 0`` ``pts`` is non-differentiable and the depth receives no gradient."""
+
+    @staticmethod
+    def forward(ctx, depth_pred, img_feats, Kc, Rc, tc, ref_img, edge_ofs, edge_src, geom):
+        img_size, offset, n = geom
+        pts, var = lightningmodel.backproject_variance(depth_pred, img_feats, Rc, tc, Kc, None, img_size, offset=offset, n=n,
+                                                       csr=(None, ref_img, edge_ofs, edge_src))
+        # the depth map is a few hundred KB: its clone keeps the reference's `depth_pred += offset_pred` legal between forward
+        # and backward.  Nothing of size E * C * n_hyp * P is kept.
+        ctx.save_for_backward(img_feats, depth_pred.detach().clone(), Kc, Rc, tc, ref_img, edge_ofs, edge_src)
+        ctx.geom = geom
+        ctx.set_materialize_grads(False)
+        if n > 0:
+            ctx.mark_non_differentiable(pts)
+        return pts, var
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_pts, grad_var):
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return (None,) * 9
+        img_size, offset, n = ctx.geom
+        # only the pair(s) needed: an output the loss does not use arrives as None (set_materialize_grads(False))
+        want_depth = ctx.needs_input_grad[0] and n == 0 and grad_pts is not None
+        want_feat = ctx.needs_input_grad[1] and grad_var is not None
+        if not (want_depth or want_feat):
+            return (None,) * 9
+        img_feats, depth, Kc, Rc, tc, ref_img, edge_ofs, edge_src = ctx.saved_tensors
+        lib = _lib.load()
+        dev = img_feats.device
+        n_img, C, Hf, Wf = img_feats.shape
+        n_ref, h, w = depth.shape
+        rows = n_ref * h * w
+        feat_cl = img_feats.detach().float().permute(0, 2, 3, 1).contiguous()
+        d = depth.float().contiguous()
+        grad_cl = grad_depth = None
+        # a .sum() upstream hands autograd a stride-0 expanded tensor, a slice a non-contiguous one
+        if want_feat:
+            grad_var = grad_var.float().contiguous()
+            assert grad_var.shape == (rows, 2 * n + 1, C)
+            grad_cl = torch.empty((n_img, Hf, Wf, C), dtype=torch.float32, device=dev)     # zero-filled by the call
+        if want_depth:
+            grad_pts = grad_pts.float().contiguous()
+            assert grad_pts.shape == (rows, 1, 3)
+            grad_depth = torch.empty((n_ref, h, w), dtype=torch.float32, device=dev)       # every element is written
+        with torch.cuda.device(dev):
+            rc = lib.v3d_backproject_variance_backward_f32(
+                _lib.ptr(d), _lib.ptr(feat_cl), _lib.ptr(Kc), _lib.ptr(Rc), _lib.ptr(tc), _lib.ptr(ref_img), _lib.ptr(edge_ofs),
+                _lib.ptr(edge_src), n_img, n_ref, edge_src.shape[0], C, Hf, Wf, int(img_size[0]), int(img_size[1]), h, w,
+                float(offset), int(n), _lib.ptr(grad_var if want_feat else None), _lib.ptr(grad_pts if want_depth else None),
+                _lib.ptr(grad_cl), _lib.ptr(grad_depth), _lib.stream_ptr(dev))
+        _lib.check(rc, 'v3d_backproject_variance_backward_f32')
+        return (grad_depth.to(depth.dtype) if want_depth else None,
+                grad_cl.permute(0, 3, 1, 2).to(img_feats.dtype) if want_feat else None) + (None,) * 7
+
+
+def backproject_variance(depth_pred, img_feats, rotmats, tvecs, K, ref_src_edges, img_size, offset=0.0, n=0, csr=None):
+    """Rows B1-B2 / C1 as a differentiable function: -> ``(pts [n_ref*P, 2n+1, 3], var [n_ref*P, 2n+1, C])`` of
+    ``lightningmodel.backproject_variance``, bit for bit.  ``var`` is differentiable with respect to ``img_feats`` [n_img, C, Hf,
+    Wf] (C in {16, 32}); with ``n == 0`` ``pts`` is differentiable with respect to ``depth_pred`` [n_ref, h, w].  ``csr``: the
+    result of ``mvsnet.edges_to_csr(ref_src_edges)`` when the caller holds it."""
+    mvsnet._require_cuda(depth_pred, 'training.backproject_variance')
+    mvsnet._require_cuda(img_feats, 'training.backproject_variance')
+    dev = depth_pred.device
+    if csr is None:
+        csr = mvsnet.edges_to_csr(ref_src_edges.to(dev))
+    _, ref_img, edge_ofs, edge_src = csr
+    Kc, Rc, tc = (x.detach().to(dev).contiguous().float() for x in (K, rotmats, tvecs))
+    geom = ((int(img_size[0]), int(img_size[1])), float(offset), int(n))
+    return BackprojectVariance.apply(depth_pred, img_feats, Kc, Rc, tc, ref_img, edge_ofs, edge_src, geom)
+
+
+def _pts_batch(depth_pred, depth_batch):
+    n_ref, h, w = depth_pred.shape
+    return depth_batch.unsqueeze(1).expand(n_ref, h * w).reshape(-1)
+
+
+def feature_rich_pointcloud(depth_pred, depth_batch, img_feats, rotmats, tvecs, K, ref_src_edges, img_size, csr=None):
+    """The differentiable twin of ``PL3DVNet.construct_feature_rich_pointcloud`` (lightningmodel.py:132-174) -> ``(pts [Np, 3],
+    pts_feat [Np, C], pts_batch [Np])``: ``pts`` carries the gradient to ``depth_pred``, ``pts_feat`` to ``img_feats``."""
+    pts, var = backproject_variance(depth_pred, img_feats, rotmats, tvecs, K, ref_src_edges, img_size, csr=csr)
+    return pts.view(-1, 3), var.view(-1, var.shape[-1]), _pts_batch(depth_pred, depth_batch)
+
+
+def pointflow_hypotheses(depth_pred, depth_batch, img_feats, rotmats, tvecs, K, ref_src_edges, offset, n, img_size, csr=None):
+    """The hypothesis points and features of ``run_pointflow`` (lightningmodel.py:187-235) -> ``(pts_hyp [Np, 2n+1, 3], pts_feat
+    [Np, 2n+1, C], pts_batch [Np])``.  The gradient reaches ``img_feats`` only: the reference builds ``pts_hyp`` and the grid
+    under ``no_grad``."""
+    pts_hyp, pts_feat = backproject_variance(depth_pred, img_feats, rotmats, tvecs, K, ref_src_edges, img_size, offset=offset,
+                                             n=n, csr=csr)
+    return pts_hyp, pts_feat, _pts_batch(depth_pred, depth_batch)
 
 
 def _conv_bn_relu(mod, x, bn_training):

@@ -950,6 +950,41 @@ int v3d_psv_variance_backward_f32(const float* feat_cl, const float* K, const fl
  * ABI version: STILL 9 (additive: a new symbol, no changed signature). */
 int v3d_psv_kernel_choice(int n_img, int C, int Hf, int Wf);
 
+/* Training, stage 2: backward of v3d_backproject_variance_f32 (csrc/backproject_backward.hip; the autograd of
+ * lightningmodel.py:132-174 and :187-235).  The reference builds the sampling grid under torch.no_grad(), so two gradients exist
+ * and no other: the variance has none with respect to depth, cameras or offset, and with n_half > 0 the points have none at all.
+ * ABI version: STILL 9 (additive: a new symbol, no changed signature).
+ *   depth        [n_ref, h, w]; K, R, t, the edge CSR and the scalar arguments are those of v3d_backproject_variance_f32
+ *   feat_cl      [n_img, Hf, Wf, C]  the features CHANNEL-LAST (the forward takes [n_img, C, Hf, Wf]);  C in {16, 32}
+ *   grad_var     [n_ref*h*w, 2 n_half + 1, C] or NULL          grad_feat_cl [n_img, Hf, Wf, C] out, NULL iff grad_var is NULL
+ *   grad_pts     [n_ref*h*w, 1, 3] or NULL, n_half == 0 only   grad_depth   [n_ref, h, w] out, NULL iff grad_pts is NULL
+ * Feature gradient.  Per reference view with cnt edges, per pixel, hypothesis and channel: x_e = bilinear sample of source e (zeros
+ *   padding), avg = sum_e x_e / cnt, and with gV = grad_var:
+ *       g_e = gV * 2 * (x_e - avg) / cnt,     grad_feat[src_e, tap, c] += w_tap * g_e   for the in-image taps.
+ *   The call zero-fills grad_feat_cl itself (the caller allocates it uninitialised), then accumulates with fp32 atomic adds whose
+ *   arrival order is not fixed: the last bits can differ between two calls with the same inputs (each element stays within the fp32
+ *   bound of its sum).  An image that appears in no edge ends with exact zeros.
+ * Depth gradient.  pts = R^T (K^-1 (p d) - t), p = (x, y, 1):  grad_depth[r, pix] = sum_j grad_pts[row, j] ray_j, ray = R^T K^-1 p.
+ *   One thread per pixel, no atomics: repeated calls are bit-identical.  Evaluation order, dot3_chain(a0, b0, a1, b1, a2, b2) =
+ *   fma(a2, b2, fma(a1, b1, a0 * b0)):
+ *       c_i   = dot3_chain(Kinv[i,0], x, Kinv[i,1], y, Kinv[i,2], 1)
+ *       ray_j = dot3_chain(R[0,j], c_0, R[1,j], c_1, R[2,j], c_2)
+ *       g     = dot3_chain(gp_0, ray_0, gp_1, ray_1, gp_2, ray_2)
+ *   Kinv is the forward's (fp64 adjugate / determinant, rounded to fp32); x, y are the forward's grid coordinates
+ *   (float)(gx * x_step), x_step = (W - 1) / (w - 1) in double, the last column and row pinned to W - 1 and H - 1.
+ * Sample positions: the forward's, bit for bit -- hypothesis depth depth + (float)((double)(hyp - n_half) * offset), the same device
+ *   functions after it.  A NaN or out-of-range position has no valid tap: it contributes x_e = 0 and receives nothing.
+ * No scratch memory: the call takes none, allocates nothing and never synchronises; asynchronous on `stream`.
+ * Host-side errors, all before anything is enqueued and before either output is touched: V3D_ERR_BAD_ARG (a null depth, feat_cl,
+ *   camera or edge pointer; a grad pair with one side set; neither pair set; grad_pts with n_half > 0), V3D_ERR_UNSUPPORTED (C),
+ *   V3D_ERR_BAD_SHAPE (a size that is not positive, H <= 1 or W <= 1, Hf or Wf > 32759, (Hf + 2) (Wf + 2) >= 2^28 - 1,
+ *   n_img Hf Wf C >= 2^31, h w >= 2^31, more than 2^31 - 1 workgroups). */
+int v3d_backproject_variance_backward_f32(const float* depth, const float* feat_cl, const float* K, const float* R, const float* t,
+                                          const int32_t* ref_img, const int32_t* edge_ofs, const int32_t* edge_src,
+                                          int n_img, int n_ref, int n_edges, int C, int Hf, int Wf, int H, int W, int h, int w,
+                                          double offset, int n_half, const float* grad_var, const float* grad_pts,
+                                          float* grad_feat_cl, float* grad_depth, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

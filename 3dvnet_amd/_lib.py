@@ -90,6 +90,9 @@ SIGNATURES = {
     'v3d_sparse_interp_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
                                       c_int, c_void_p, c_float, c_void_p, c_int, c_int, c_void_p, c_size_t,
                                       c_void_p]),
+    'v3d_sparse_interp_backward_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'v3d_sparse_interp_backward_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                               c_float, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'v3d_edges_csr_workspace_bytes': (c_size_t, [c_int, c_int]),
     'v3d_edges_csr': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'v3d_edges_csr_status': (c_int, [c_void_p, c_size_t, c_void_p]),

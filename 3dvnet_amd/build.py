@@ -93,6 +93,8 @@ def build(force=False, verbose=False, strict=False):
             # the back-projected variance's backward: the same state per hypothesis segment; the depth kernel's chains
             isa_check.check_no_scratch(os.path.join(objdir, 'backproject_backward.o'), 'backproject_[a-z]*_backward_kernel',
                                        strict=strict)
+            # the sparse interpolation's backward: the 8 slots, weights and gradient rows of a lane in flight stay in registers
+            isa_check.check_no_scratch(os.path.join(objdir, 'sparse.o'), 'interp_backward_[a-z]*_kernel', strict=strict)
             # confidence: the running maximum, the denominator and the two plane indices of a pixel stay in registers
             isa_check.check_no_scratch(os.path.join(objdir, 'confidence.o'), 'soft_argmin_prob_kernel', strict=strict)
             isa_check.check_no_scratch(os.path.join(objdir, 'confidence.o'), 'prob_gather_kernel', strict=strict)

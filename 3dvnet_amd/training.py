@@ -19,11 +19,21 @@ the image features and the stage-1 depth.  Its node saves the features, the dept
   * ``feature_rich_pointcloud``                          the differentiable twin of ``construct_feature_rich_pointcloud``;
   * ``pointflow_hypotheses``                             the hypothesis points and features of ``run_pointflow``.
 
+The consumer of those hypotheses is the hypothesis decoder (``mv3d/subnetworks/refinement.py:28-44``, ``lightningmodel.py:
+237-241``).  One piece of it has no usable stock route: the sparse trilinear interpolation, whose stock formulation materialises
+nq * 8 * C floats per level.  Its backward is ``v3d_sparse_interp_backward_f32`` (``csrc/sparse.hip``): a per-row sum through an
+inverted index of the forward's corner table, without atomics, bitwise reproducible:
+
+  * ``SparseInterpolate`` / ``sparse_interpolate``       one level at the hypothesis points -> level features;
+  * ``decoder_features``                                 the wide feature row of ``HypothesisDecoder.features``;
+  * ``hypothesis_decoder``                               Conv1d / BatchNorm1d / ReLU stack, head and softmax, functional;
+  * ``pointflow_offset``                                 hypotheses -> features -> decoder -> expected offset of ``run_pointflow``.
+
 Cameras, plane depths, offsets and edges are data (no gradient), as in the reference, which also builds every sampling grid under
-``no_grad``.  The feature gradients are summed with fp32 atomic adds: their last bits can differ from call to call (DESIGN.md
-4.1b, 4.1c).  Out of scope: the rest of stage 2 (PointNet, the sparse U-Net, the trilinear interpolation, the decoder), stage 3,
-the native backbone, the split / channel-last variance formats, ``PL3DVNet.forward`` in training mode, an optimiser loop
-(DESIGN.md 6).  No CPU fallback.
+``no_grad``.  The image-feature gradients are summed with fp32 atomic adds: their last bits can differ from call to call (DESIGN.md
+4.1b, 4.1c).  Out of scope: the rest of stage 2 (PointNet and the sparse U-Net: they connect to the level-feature gradients
+produced here), stage 3, the native backbone, the split / channel-last variance formats, ``PL3DVNet.forward`` in training mode,
+an optimiser loop.  No CPU fallback.
 """
 import torch
 import torch.nn.functional as F
@@ -179,6 +189,133 @@ def pointflow_hypotheses(depth_pred, depth_batch, img_feats, rotmats, tvecs, K, 
     pts_hyp, pts_feat = backproject_variance(depth_pred, img_feats, rotmats, tvecs, K, ref_src_edges, img_size, offset=offset,
                                              n=n, csr=csr)
     return pts_hyp, pts_feat, _pts_batch(depth_pred, depth_batch)
+
+
+def _level_min_pts(x):
+    """scatter(x.pts, x.batch, reduce='min') (refinement.py:33), cached on the level dict as ``HypothesisDecoder.features`` does."""
+    if '_min_pts' not in x:
+        nb = int(x['batch'].max().item()) + 1
+        x['_min_pts'] = torch.stack([x['pts'][x['batch'] == b].amin(dim=0) for b in range(nb)]) \
+            if nb > 1 else x['pts'].amin(dim=0, keepdim=True)
+    return x['_min_pts']
+
+
+class SparseInterpolate(torch.autograd.Function):
+    """``v3d_sparse_interp_f32`` (``MinkowskiInterpolation``, refinement.py:26,39) -> [n_pts, n_hyp, C] with its one gradient,
+    to the level features: ``v3d_sparse_interp_backward_f32`` (no atomics, bitwise reproducible).  The node
+    saves the queries, their batch indices, ``min_pts`` and the hash table: 12 bytes per query, nothing of size nq * 8 * C."""
+
+    @staticmethod
+    def forward(ctx, feats, pts, pts_batch, table, min_pts, geom):
+        n_in, stride, res = geom
+        lib = _lib.load()
+        dev = pts.device
+        n_pts, n_hyp = pts.shape[:2]
+        f = feats.detach().float().contiguous()
+        assert f.shape[0] == n_in
+        C = f.shape[1]
+        out = torch.empty((n_pts, n_hyp, C), dtype=torch.float32, device=dev)
+        ws = torch.empty(lib.v3d_sparse_interp_workspace_bytes(n_pts, n_hyp), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.v3d_sparse_interp_f32(_lib.ptr(table), n_in, _lib.ptr(f), C, stride, _lib.ptr(pts), _lib.ptr(pts_batch),
+                                           n_pts, n_hyp, _lib.ptr(min_pts), res, _lib.ptr(out), C, 0, _lib.ptr(ws), ws.numel(),
+                                           _lib.stream_ptr(dev))
+        _lib.check(rc, 'v3d_sparse_interp_f32')
+        ctx.save_for_backward(pts, pts_batch, table, min_pts)
+        ctx.geom = geom
+        ctx.feats_meta = (C, feats.dtype)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        pts, pts_batch, table, min_pts = ctx.saved_tensors
+        n_in, stride, res = ctx.geom
+        C, dtype = ctx.feats_meta
+        lib = _lib.load()
+        dev = pts.device
+        n_pts, n_hyp = pts.shape[:2]
+        assert grad_out.shape == (n_pts, n_hyp, C)
+        # the backward of `cat` hands out a view of the wide feature row: its own row stride is passed on (ld_grad) instead of
+        # copying it.  Anything else (a stride-0 expanded tensor of a .sum(), a transposed view) becomes one contiguous copy.
+        g = grad_out
+        st = g.stride()
+        strided = g.dtype == torch.float32 and n_pts * n_hyp > 0 and st[2] == 1 and st[1] >= C and st[0] == n_hyp * st[1]
+        if not strided:
+            g = g.float().contiguous()
+        ld = g.stride(1)
+        grad_feats = torch.empty((n_in, C), dtype=torch.float32, device=dev)        # every element is written
+        ws = torch.empty(lib.v3d_sparse_interp_backward_workspace_bytes(n_in, C, n_pts, n_hyp), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.v3d_sparse_interp_backward_f32(_lib.ptr(table), n_in, C, stride, _lib.ptr(pts), _lib.ptr(pts_batch), n_pts,
+                                                    n_hyp, _lib.ptr(min_pts), res, g.data_ptr(), ld, 0, _lib.ptr(grad_feats),
+                                                    _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+        _lib.check(rc, 'v3d_sparse_interp_backward_f32')
+        return (grad_feats.to(dtype),) + (None,) * 5
+
+
+def sparse_interpolate(x, pts, pts_batch, feats=None):
+    """Sparse trilinear interpolation of one level of ``SparseUNet.forward`` (``x``: its dict with ``'sparse'``, ``'stride'``,
+    ``'res'``, ``'pts'``, ``'batch'``) at ``pts`` [n_pts, n_hyp, 3] -> [n_pts, n_hyp, C]: the bits of the corresponding columns
+    of ``HypothesisDecoder.features``, differentiable in ``feats`` [N, C] (default ``x['feats']``; a leaf or the output of a
+    differentiable U-Net).  ``pts`` and ``pts_batch`` [n_pts] are data: the reference builds the hypotheses under ``no_grad``."""
+    mvsnet._require_cuda(pts, 'training.sparse_interpolate')
+    feats = x['feats'] if feats is None else feats
+    mvsnet._require_cuda(feats, 'training.sparse_interpolate')
+    lv = x['sparse']
+    assert feats.dim() == 2 and feats.shape[0] == lv.n, (tuple(feats.shape), lv.n)
+    pts = pts.detach().contiguous().float()
+    pts_batch = pts_batch.contiguous().long()
+    min_pts = _level_min_pts(x).detach().contiguous().float()
+    return SparseInterpolate.apply(feats, pts, pts_batch, lv.table, min_pts, (int(lv.n), int(x['stride']), float(x['res'])))
+
+
+def decoder_features(xs, pts, pts_feat, pts_batch, level_feats=None):
+    """Row C2a as a differentiable function -> [n_pts, n_hyp, in_dim] in the layout (and with the bits) of
+    ``HypothesisDecoder.features``: finest level first, ``pts_feat`` last (refinement.py:32-41).  ``xs``: the levels of
+    ``SparseUNet.forward``, coarse to fine; ``level_feats``: one [N_l, C_l] tensor per level in the order of ``xs`` (default
+    ``x['feats']``).  Differentiable in the level features and in ``pts_feat`` (None: no point features)."""
+    if level_feats is None:
+        level_feats = [None] * len(xs)
+    assert len(level_feats) == len(xs)
+    features = pts_feat
+    for x, f in zip(xs, level_feats):
+        feats = sparse_interpolate(x, pts, pts_batch, f)
+        features = feats if features is None else torch.cat((feats, features.to(feats.dtype)), dim=2)
+    return features
+
+
+def hypothesis_decoder(decoder, features, bn_training=False):
+    """The Conv1d + BatchNorm1d + ReLU stack, the Conv1d head and the softmax of ``HypothesisDecoder.forward``
+    (refinement.py:42-43) with stock differentiable torch ops over the parameters and buffers of an existing
+    ``refinement.HypothesisDecoder`` (no second parameter set; its ``state_dict`` keys are untouched).  features [n_pts, n_hyp,
+    in_dim] -> preds [n_pts, n_hyp].  ``bn_training`` as in ``costregnet``."""
+    y = features.transpose(2, 1)
+    for i in range(3):
+        conv, bn = decoder.net[i][0], decoder.net[i][1]
+        y = F.conv1d(y, conv.weight, None, stride=conv.stride, padding=conv.padding)
+        y = F.batch_norm(y, bn.running_mean, bn.running_var, bn.weight, bn.bias, training=bn_training, momentum=bn.momentum,
+                         eps=bn.eps)
+        y = F.relu(y)
+    head = decoder.net[3]
+    y = F.conv1d(y, head.weight, head.bias, stride=head.stride, padding=head.padding)
+    return F.softmax(y.squeeze(1), dim=1)
+
+
+def pointflow_offset(decoder, xs, depth_pred, depth_batch, img_feats, rotmats, tvecs, K, ref_src_edges, offset, n, img_size,
+                     level_feats=None, bn_training=False, csr=None):
+    """``run_pointflow`` (lightningmodel.py:187-242) as a differentiable function -> the expected offset [n_ref, h, w]; the caller
+    forms ``depth_pred + offset`` and applies ``masked_mae`` (lightningmodel.py:70-79).  The gradient reaches the level
+    features (``level_feats``, default each ``x['feats']``), ``img_feats`` (through the point features) and every parameter of
+    ``decoder``; none reaches ``depth_pred``: the hypotheses are data."""
+    pts_hyp, pts_feat, pts_batch = pointflow_hypotheses(depth_pred, depth_batch, img_feats, rotmats, tvecs, K, ref_src_edges,
+                                                        offset, n, img_size, csr=csr)
+    features = decoder_features(xs, pts_hyp, pts_feat, pts_batch, level_feats=level_feats)
+    preds = hypothesis_decoder(decoder, features, bn_training=bn_training)
+    offset_vals = torch.linspace(-n * offset, n * offset, 2 * n + 1).to(preds)       # on the CPU, then moved (:238-240)
+    return torch.sum(offset_vals.unsqueeze(0) * preds, dim=1).view(depth_pred.shape)
 
 
 def _conv_bn_relu(mod, x, bn_training):

@@ -366,6 +366,18 @@ int v3d_sparse_interp_f32(const void* table, int n_in, const float* feats, int C
                           const float* pts, const int64_t* pts_batch, int n_pts, int n_hyp,
                           const float* min_pts, float res, float* out, int ld_out, int col0,
                           void* workspace, size_t workspace_bytes, void* stream);
+/* The adjoint of v3d_sparse_interp_f32 with respect to feats (training):
+ *   grad_feats[r, c] = sum over the corner slots (q, k) with row(q, k) == r of w(q, k) * grad_out[q * ld_grad + col0 + c],
+ * row(q, k) and w(q, k) being the forward's corner table (the same kernel fills it).  grad_feats [n_in, C] (16-byte aligned):
+ * EVERY element is written, rows nobody touches as +0.  No float atomics: the corner slots are grouped by row (stable) and each
+ * row's list is summed in list order, lists of more than 512 slots in chunks of 512 whose partial sums are added in chunk order;
+ * the result is bitwise reproducible from call to call.  No step synchronises with the host.  The same C, n_pts * n_hyp * 8 < 2^31
+ * and error codes as the forward; ld_grad >= col0 + C; n_pts == 0 zero-fills grad_feats (the workspace may then be null). */
+size_t v3d_sparse_interp_backward_workspace_bytes(int n_in, int C, int n_pts, int n_hyp);
+int v3d_sparse_interp_backward_f32(const void* table, int n_in, int C, int tensor_stride, const float* pts,
+                                   const int64_t* pts_batch, int n_pts, int n_hyp, const float* min_pts, float res,
+                                   const float* grad_out, int ld_grad, int col0, float* grad_feats, void* workspace,
+                                   size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Row B3 (mv3d/utils.py:38-64 incl. the un-vendored torch_geometric voxel_grid / torch_cluster grid,

@@ -1,6 +1,6 @@
 // Device functions shared by the plane-sweep kernels (the forward family mapped in psv_variance.hip: warp + variance, sample
-// positions; psv_backward.hip: the gradient of the variance with respect to the features).  Together with v3d::world_point and
-// v3d::sample_position (v3d_common.h) they are the ONE statement of the sample geometry: the camera blocks, the plane-sweep
+// positions) and by the backward walk of variance_backward.h (the gradient of a variance over the edges with respect to the
+// features: psv_backward.hip, backproject_backward.hip).  Together with v3d::world_point and v3d::sample_position (v3d_common.h) they are the ONE statement of the sample geometry: the camera blocks, the plane-sweep
 // grid, and the bilinear footprint of a sample position.  A kernel that includes this header and calls them sees the
 // positions and weights of every other, bit for bit.
 #pragma once

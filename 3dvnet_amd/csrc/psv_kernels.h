@@ -1,6 +1,6 @@
 // What the translation units of the plane-sweep warp + variance share (psv_variance.hip is the map of the family): the launch
 // parameters, the tap record of a sample, the constants of the 8-pixel x 8-plane wave, the epilogue helpers, and every unit's
-// launcher.  The sample geometry itself is psv_common.h's, which the backward (psv_backward.hip) shares.
+// launcher.  The sample geometry itself is psv_common.h's, which the backward walk (variance_backward.h) shares.
 #pragma once
 #include "bf16_split.h"
 #include "psv_common.h"

@@ -4,7 +4,7 @@
 //
 // This file is the host side of the operation -- workspace plan, argument validation, the choice of the warp kernel and the
 // extern "C" entry points -- and the map of its kernels, one unit per translation unit (psv_kernels.h declares what they share
-// and their launchers; psv_common.h states the sample geometry, which the backward, psv_backward.hip, shares):
+// and their launchers; psv_common.h states the sample geometry, which the backward walk, variance_backward.h, shares):
 //
 //   psv_prepare.hip    feat [n_img, C, Hf, Wf] -> featT [n_img, Hf + 2, Wf + 2, C] (workspace): channel-last, so that one bilinear
 //                      tap of all C channels is one contiguous run, with a border of zero cells, so that grid_sample's zero

@@ -42,6 +42,23 @@ from torch.autograd.function import once_differentiable
 from . import _lib, lightningmodel, mvsnet
 
 
+def _feature_gradient(features, grad_var, shape, call):
+    """The feature-gradient plumbing both backward passes share.  ``features`` [n_img, C, Hf, Wf] of any float dtype and layout go
+    in as a channel-last fp32 copy; ``grad_var`` (or None: no feature gradient is wanted) as an fp32 contiguous copy of ``shape``;
+    ``call(feat_cl, grad_var, grad_cl)`` runs the entry point, which zero-fills the target ``grad_cl`` [n_img, Hf, Wf, C] itself (None
+    with ``grad_var``); -> the gradient in the shape and dtype of ``features``, or None."""
+    n_img, C, Hf, Wf = features.shape
+    feat_cl = features.detach().float().permute(0, 2, 3, 1).contiguous()
+    grad_cl = None
+    if grad_var is not None:
+        # a .sum() upstream hands autograd a stride-0 expanded tensor, a slice a non-contiguous one
+        grad_var = grad_var.float().contiguous()
+        assert grad_var.shape == shape
+        grad_cl = torch.empty((n_img, Hf, Wf, C), dtype=torch.float32, device=features.device)
+    call(feat_cl, grad_var, grad_cl)
+    return None if grad_cl is None else grad_cl.permute(0, 3, 1, 2).to(features.dtype)
+
+
 class PlaneSweepVariance(torch.autograd.Function):
     """``mvsnet.plane_sweep_variance`` (the same kernel: the same bits) with a backward with respect to the features."""
 
@@ -65,19 +82,16 @@ class PlaneSweepVariance(torch.autograd.Function):
         dev = features_quarter.device
         n_img, C, Hf, Wf = features_quarter.shape
         h, w = depth_img_size
-        feat_cl = features_quarter.detach().float().permute(0, 2, 3, 1).contiguous()
-        # a .sum() upstream hands autograd a stride-0 expanded tensor, a slice a non-contiguous one
-        grad_var = grad_var.float().contiguous()
-        assert grad_var.shape == (ref_img.shape[0], C, n_planes, h, w)
-        grad_cl = torch.empty((n_img, Hf, Wf, C), dtype=torch.float32, device=dev)      # zero-filled by the call
-        with torch.cuda.device(dev):
-            rc = lib.v3d_psv_variance_backward_f32(
-                _lib.ptr(feat_cl), _lib.ptr(Kc), _lib.ptr(Rc), _lib.ptr(tc), _lib.ptr(ref_img), _lib.ptr(edge_ofs),
-                _lib.ptr(edge_src), n_img, ref_img.shape[0], edge_src.shape[0], C, Hf, Wf, int(img_size[0]), int(img_size[1]),
-                float(depth_start), float(depth_interval), int(n_planes), int(h), int(w), _lib.ptr(grad_var),
-                _lib.ptr(grad_cl), _lib.stream_ptr(dev))
-        _lib.check(rc, 'v3d_psv_variance_backward_f32')
-        return (grad_cl.permute(0, 3, 1, 2).to(features_quarter.dtype),) + (None,) * 7
+
+        def call(feat_cl, grad_var, grad_cl):
+            with torch.cuda.device(dev):
+                rc = lib.v3d_psv_variance_backward_f32(
+                    _lib.ptr(feat_cl), _lib.ptr(Kc), _lib.ptr(Rc), _lib.ptr(tc), _lib.ptr(ref_img), _lib.ptr(edge_ofs),
+                    _lib.ptr(edge_src), n_img, ref_img.shape[0], edge_src.shape[0], C, Hf, Wf, int(img_size[0]), int(img_size[1]),
+                    float(depth_start), float(depth_interval), int(n_planes), int(h), int(w), _lib.ptr(grad_var),
+                    _lib.ptr(grad_cl), _lib.stream_ptr(dev))
+            _lib.check(rc, 'v3d_psv_variance_backward_f32')
+        return (_feature_gradient(features_quarter, grad_var, (ref_img.shape[0], C, n_planes, h, w), call),) + (None,) * 7
 
 
 def plane_sweep_variance(features_quarter, rotmats, tvecs, K, ref_src_edges, depth_start, depth_interval, n_planes, img_size,
@@ -131,27 +145,23 @@ class BackprojectVariance(torch.autograd.Function):
         n_img, C, Hf, Wf = img_feats.shape
         n_ref, h, w = depth.shape
         rows = n_ref * h * w
-        feat_cl = img_feats.detach().float().permute(0, 2, 3, 1).contiguous()
         d = depth.float().contiguous()
-        grad_cl = grad_depth = None
-        # a .sum() upstream hands autograd a stride-0 expanded tensor, a slice a non-contiguous one
-        if want_feat:
-            grad_var = grad_var.float().contiguous()
-            assert grad_var.shape == (rows, 2 * n + 1, C)
-            grad_cl = torch.empty((n_img, Hf, Wf, C), dtype=torch.float32, device=dev)     # zero-filled by the call
+        grad_depth = None
         if want_depth:
-            grad_pts = grad_pts.float().contiguous()
+            grad_pts = grad_pts.float().contiguous()            # stride-0 or sliced, as grad_var (_feature_gradient)
             assert grad_pts.shape == (rows, 1, 3)
             grad_depth = torch.empty((n_ref, h, w), dtype=torch.float32, device=dev)       # every element is written
-        with torch.cuda.device(dev):
-            rc = lib.v3d_backproject_variance_backward_f32(
-                _lib.ptr(d), _lib.ptr(feat_cl), _lib.ptr(Kc), _lib.ptr(Rc), _lib.ptr(tc), _lib.ptr(ref_img), _lib.ptr(edge_ofs),
-                _lib.ptr(edge_src), n_img, n_ref, edge_src.shape[0], C, Hf, Wf, int(img_size[0]), int(img_size[1]), h, w,
-                float(offset), int(n), _lib.ptr(grad_var if want_feat else None), _lib.ptr(grad_pts if want_depth else None),
-                _lib.ptr(grad_cl), _lib.ptr(grad_depth), _lib.stream_ptr(dev))
-        _lib.check(rc, 'v3d_backproject_variance_backward_f32')
-        return (grad_depth.to(depth.dtype) if want_depth else None,
-                grad_cl.permute(0, 3, 1, 2).to(img_feats.dtype) if want_feat else None) + (None,) * 7
+
+        def call(feat_cl, grad_var, grad_cl):
+            with torch.cuda.device(dev):
+                rc = lib.v3d_backproject_variance_backward_f32(
+                    _lib.ptr(d), _lib.ptr(feat_cl), _lib.ptr(Kc), _lib.ptr(Rc), _lib.ptr(tc), _lib.ptr(ref_img), _lib.ptr(edge_ofs),
+                    _lib.ptr(edge_src), n_img, n_ref, edge_src.shape[0], C, Hf, Wf, int(img_size[0]), int(img_size[1]), h, w,
+                    float(offset), int(n), _lib.ptr(grad_var), _lib.ptr(grad_pts if want_depth else None), _lib.ptr(grad_cl),
+                    _lib.ptr(grad_depth), _lib.stream_ptr(dev))
+            _lib.check(rc, 'v3d_backproject_variance_backward_f32')
+        grad_feats = _feature_gradient(img_feats, grad_var if want_feat else None, (rows, 2 * n + 1, C), call)
+        return (grad_depth.to(depth.dtype) if want_depth else None, grad_feats) + (None,) * 7
 
 
 def backproject_variance(depth_pred, img_feats, rotmats, tvecs, K, ref_src_edges, img_size, offset=0.0, n=0, csr=None):

@@ -27,7 +27,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-SEG = 16          # planes a wave of the backward kernel walks (csrc/psv_backward.hip: kBDS)
+SEG = 16          # planes a wave of the backward kernel walks (csrc/psv_backward.hip: kBDS, the S of variance_backward.h's walk)
 
 
 def timed(fn, warmup, repeats):

@@ -1,12 +1,13 @@
 """Float64 oracle of the two gradients of the back-projected variance (csrc/backproject_backward.hip): var -> features and, for
-n = 0, pts -> depth.  TEST HELPER, no product code.  Modelled on tests/psv_backward_oracle.py, whose taps, bound and cases it reuses.
+n = 0, pts -> depth.  TEST HELPER, no product code.  The feature gradient is tests/psv_backward_oracle.py's core (variance_gradient: both
+kernels are one walk, csrc/variance_backward.h) on this operation's positions; its taps, bound and cases are reused as well.
 
 The sample positions are the fp32 positions of ``oracle/pinned.py`` (``backproject_points`` at depth + i * offset for i = -n .. n,
 then ``sample_positions``: the orders the forward kernel implements bit for bit), promoted to float64; everything after them is
 float64.  Layouts: ``gvar`` [n_ref * P, n_hyp, C], ``gpts`` [n_ref * P, 1, 3], the sample index within a reference is
 pixel * n_hyp + hypothesis.
 
-``gradient`` returns g64, N, M, cnt_max exactly as ``pbo.gradient`` defines them, so ``pbo.bound`` -- (N + 32 + max(0, cnt_max - 9))
+``gradient`` returns g64, N, M, cnt_max of ``pbo.variance_gradient``, so ``pbo.bound`` -- (N + 32 + max(0, cnt_max - 9))
 2^-24 M -- and ``pbo.violations`` apply; the derivation in ``pbo.bound``'s docstring carries over term for term (the hypothesis axis
 plays the role of the plane axis).  ``depth_gradient`` returns (g64, M_d) with M_d = sum_j |gp_j| sum_i |R_ij| sum_k |Kinv_ik| |p_k|;
 its bound is 16 * 2^-24 * M_d: nine roundings in three nested 3-term chains, plus slack.
@@ -20,8 +21,7 @@ import psv_backward_oracle as pbo
 from oracle import pinned as pin
 
 U = pbo.U
-CHUNK = 8               # edges whose tap records the kernel keeps in LDS at a time (backproject_backward.hip: kBMaxE)
-SEGMENT = 8             # hypotheses per workgroup with n > 0
+SEGMENT = 8             # hypotheses per workgroup with n > 0 (csrc/backproject_backward.hip: the S of its launch)
 CASES = [(C, cam, n) for n in (3, 0) for C, cam in ((16, 'rotated'), (32, 'rotated'), (32, 'sliding'))]
 CHUNK_CASES = [('chunk', C, cam, 4) for C in (16, 32) for cam in ('rotated', 'dense')]
 SEGMENT_CASES = [('chunk', 32, 'dense', n) for n in (0, 1, 3, 7, 8, 16)]      # 1, 3, 7, 15, 17, 33 hypotheses
@@ -101,13 +101,13 @@ def _per_ref(gvar, n_ref, C):
 
 
 def gradient(case, gvar=None, variant=None, dtype=torch.float64):
-    """-> dict(g64, N, M) [n_img, C, Hf, Wf] and cnt_max, as pbo.gradient.  ``dtype=torch.float32``: the same taps and weights
-    evaluated with float32 torch ops (g64 is then that float32 gradient; N and M stay float64).
-    variant: None | pbo's 'no_avg', 'global_cnt', 'swap_ne_sw', 'avg_first_chunk', 'drop_later_chunks', 'stale_records' |
+    """-> dict(g64, N, M) [n_img, C, Hf, Wf] and cnt_max, as pbo.gradient: pbo.variance_gradient on this operation's positions and
+    upstream gradient.  ``dtype=torch.float32``: the same taps and weights evaluated with float32 torch ops (g64 is then that
+    float32 gradient; N and M stay float64).
+    variant: None | the variants of pbo.variance_gradient | the bugs along the hypothesis axis:
       'tail_hyp'       the last hypothesis contributes nothing;     'centre_only'   only hypothesis n contributes;
       'reversed_hyp'   gvar is applied in reverse hypothesis order;  'first_segment' hypotheses >= 8 contribute nothing."""
-    feat = case['feat'].double()
-    n_img, C, Hf, Wf = feat.shape
+    C = case['feat'].shape[1]
     n_hyp = 2 * case['n'] + 1
     gv = (case['gvar'] if gvar is None else gvar).double().clone()
     if variant == 'tail_hyp':
@@ -120,52 +120,13 @@ def gradient(case, gvar=None, variant=None, dtype=torch.float64):
     elif variant == 'reversed_hyp':
         gv = gv.flip(1)
     n_ref = len(torch.unique(case['edges'][0]))
-    gv = _per_ref(gv, n_ref, C)
-    flat, aflat = feat.reshape(n_img, C, Hf * Wf), feat.abs().reshape(n_img, C, Hf * Wf)
-    g, M = torch.zeros_like(flat).to(dtype), torch.zeros_like(flat)
-    N = torch.zeros((n_img, Hf * Wf), dtype=torch.float64)
-    pos = positions(case)
-    cnt_max = 0
-    for r in range(n_ref):
-        mine = [p for p in pos if p[0] == r]
-        cnt_max = max(cnt_max, len(mine))
-        cnt = float(len(pos) if variant == 'global_cnt' else len(mine))
-        taps = [pbo._taps(ix, iy, Hf, Wf) for _, _, ix, iy in mine]
-        if variant == 'swap_ne_sw':
-            taps = [[tp[0], (tp[1][0], tp[2][1], tp[2][2]), (tp[2][0], tp[1][1], tp[1][2]), tp[3]] for tp in taps]
-        if variant == 'stale_records':
-            taps = [taps[k % CHUNK] if k >= CHUNK else tp for k, tp in enumerate(taps)]
-        fl = flat.to(dtype)
-        xs = [sum(w[None].to(dtype) * fl[src][:, idx] for w, idx, _ in tp) for (_, src, _, _), tp in zip(mine, taps)]
-        As = [sum(w[None] * aflat[src][:, idx] for w, idx, _ in tp) for (_, src, _, _), tp in zip(mine, taps)]
-        avg, Aavg = sum(xs[:CHUNK] if variant == 'avg_first_chunk' else xs) / cnt, sum(As) / cnt
-        for k, ((_, src, _, _), tp, x, A) in enumerate(zip(mine, taps, xs, As)):
-            if variant == 'drop_later_chunks' and k >= CHUNK:
-                continue
-            ge = gv[r].to(dtype) * 2.0 * (x if variant == 'no_avg' else x - avg) / cnt
-            me = gv[r].abs() * (2.0 / cnt) * (A + Aavg)
-            for w, idx, ok in tp:
-                g[src].index_add_(1, idx, w[None].to(dtype) * ge)
-                M[src].index_add_(1, idx, w[None] * me)
-                N[src].index_add_(0, idx, ok.double())
-    shape = (n_img, C, Hf, Wf)
-    return dict(g64=g.reshape(shape), M=M.reshape(shape), N=N[:, None].expand(n_img, C, Hf * Wf).reshape(shape).clone(),
-                cnt_max=cnt_max)
+    return pbo.variance_gradient(positions(case), _per_ref(gv, n_ref, C), case['feat'], variant, dtype)
 
 
 def affected_images(case, variant):
-    """bool [n_img]: the images whose gradient a wrong-gradient variant can change -- the chunk bugs as in pbo.affected_images,
-    every other variant all sources of a reference (with 'no_avg' and the hypothesis variants a one-edge reference changes nothing:
-    its gradient is zero either way, and zero elements are not counted)."""
-    pos = positions(case)
-    mask = torch.zeros(case['feat'].shape[0], dtype=torch.bool)
-    for r in sorted({p[0] for p in pos}):
-        srcs = [p[1] for p in pos if p[0] == r]
-        if variant not in ('avg_first_chunk', 'drop_later_chunks', 'stale_records'):
-            mask[srcs] = True
-        elif len(srcs) > CHUNK:
-            mask[srcs if variant == 'avg_first_chunk' else srcs[CHUNK:]] = True
-    return mask
+    """pbo.affected_images over this operation's positions (with 'no_avg' and the hypothesis variants a one-edge reference changes
+    nothing: its gradient is zero either way, and zero elements are not counted)."""
+    return pbo.affected_images(case, variant, positions(case))
 
 
 bound = pbo.bound

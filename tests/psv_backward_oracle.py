@@ -23,8 +23,8 @@ from oracle import pinned as pin
 
 U = 2.0 ** -24          # unit roundoff of fp32
 CASES = [(16, 'rotated'), (32, 'rotated'), (32, 'sliding')]      # (C, cameras) of make_case
-CHUNK = 8               # edges whose tap records the kernel keeps in LDS at a time (psv_backward.hip: kBMaxE)
-SEGMENT = 16            # depth planes per workgroup (kBDS)
+CHUNK = 8               # edges whose tap records both kernels keep in LDS at a time (csrc/variance_backward.h: kBwdMaxE)
+SEGMENT = 16            # depth planes per workgroup (csrc/psv_backward.hip: kBDS)
 CHUNK_CASES = [('chunk', 16, 'rotated'), ('chunk', 16, 'dense'), ('chunk', 32, 'rotated'), ('chunk', 32, 'dense')]
 CHUNK_VARIANTS = ('avg_first_chunk', 'drop_later_chunks', 'stale_records', 'first_segment', 'tail_plane')
 
@@ -143,26 +143,36 @@ def _taps(ix, iy, Hf, Wf):
 def gradient(case, gvar=None, variant=None):
     """-> dict(g64, N, M), each [n_img, C, Hf, Wf] float64, and cnt_max, the largest edge count of a reference.  ``gvar``
     [n_ref, C, D, h, w] (default: the case's).
-    variant: None | 'no_avg' (the -avg term dropped) | 'global_cnt' (cnt = all edges of the batch) | 'swap_ne_sw', and the bugs a
-    chunked kernel could have (chunk membership by CSR position k within the reference):
-      'avg_first_chunk'    avg is summed over positions 0 .. 7 only, then divided by the full cnt;
-      'drop_later_chunks'  edges at position 8 or higher scatter nothing;
-      'stale_records'      an edge at position k >= 8 samples (its own source image) and scatters with the taps -- weights, cells,
-                           validity -- of the edge at position k % 8;
+    variant: None | the variants of ``variance_gradient`` | the bugs along the plane axis:
       'first_segment'      planes d >= 16 contribute nothing;
       'tail_plane'         plane D - 1 contributes nothing."""
-    feat = case['feat'].double()
-    n_img, C, Hf, Wf = feat.shape
+    C = case['feat'].shape[1]
     D, n_pix = case['depth'][2], case['plane_size'][0] * case['plane_size'][1]
     gv = (case['gvar'] if gvar is None else gvar).double().reshape(-1, C, D, n_pix)
     if variant in ('first_segment', 'tail_plane'):
         gv = gv.clone()
         gv[:, :, (SEGMENT if variant == 'first_segment' else D - 1):] = 0.0
-    gv = gv.reshape(-1, C, D * n_pix)
+    return variance_gradient(positions(case), gv.reshape(-1, C, D * n_pix), case['feat'], variant)
+
+
+def variance_gradient(pos, gv, feat, variant=None, dtype=torch.float64):
+    """The core both oracles share (tests/backproject_backward_oracle.py calls it with its own positions and upstream gradient).
+    ``pos``: a positions list [(ref row r, source image, ix, iy)] in CSR order; ``gv`` [n_ref, C, samples] float64, the upstream
+    gradient in the sample order of ``pos`` (the caller has applied the variants of its own axis); ``feat`` [n_img, C, Hf, Wf].
+    -> dict(g64, N, M) and cnt_max as ``gradient`` documents.  ``dtype=torch.float32``: the same taps and weights evaluated with
+    float32 torch ops (g64 is then that float32 gradient; N and M stay float64).
+    variant: None or another name (nothing to do here) | 'no_avg' (the -avg term dropped) | 'global_cnt' (cnt = all edges of the
+    batch) | 'swap_ne_sw', and the bugs a chunked kernel could have (chunk membership by CSR position k within the reference):
+      'avg_first_chunk'    avg is summed over positions 0 .. 7 only, then divided by the full cnt;
+      'drop_later_chunks'  edges at position 8 or higher scatter nothing;
+      'stale_records'      an edge at position k >= 8 samples (its own source image) and scatters with the taps -- weights, cells,
+                           validity -- of the edge at position k % 8."""
+    feat = feat.double()
+    n_img, C, Hf, Wf = feat.shape
     flat, aflat = feat.reshape(n_img, C, Hf * Wf), feat.abs().reshape(n_img, C, Hf * Wf)
-    g64, M = torch.zeros_like(flat), torch.zeros_like(flat)
+    fl = flat.to(dtype)
+    g, M = torch.zeros_like(fl), torch.zeros_like(flat)
     N = torch.zeros((n_img, Hf * Wf), dtype=torch.float64)
-    pos = positions(case)
     cnt_max = 0
     for r in sorted({p[0] for p in pos}):
         mine = [p for p in pos if p[0] == r]
@@ -173,32 +183,33 @@ def gradient(case, gvar=None, variant=None):
             taps = [[tp[0], (tp[1][0], tp[2][1], tp[2][2]), (tp[2][0], tp[1][1], tp[1][2]), tp[3]] for tp in taps]
         if variant == 'stale_records':
             taps = [taps[k % CHUNK] if k >= CHUNK else tp for k, tp in enumerate(taps)]
-        xs = [sum(w[None] * flat[src][:, idx] for w, idx, _ in tp) for (_, src, _, _), tp in zip(mine, taps)]
+        xs = [sum(w[None].to(dtype) * fl[src][:, idx] for w, idx, _ in tp) for (_, src, _, _), tp in zip(mine, taps)]
         As = [sum(w[None] * aflat[src][:, idx] for w, idx, _ in tp) for (_, src, _, _), tp in zip(mine, taps)]
         avg, Aavg = sum(xs[:CHUNK] if variant == 'avg_first_chunk' else xs) / cnt, sum(As) / cnt
         for k, ((_, src, _, _), tp, x, A) in enumerate(zip(mine, taps, xs, As)):
             if variant == 'drop_later_chunks' and k >= CHUNK:
                 continue
-            ge = gv[r] * 2.0 * (x if variant == 'no_avg' else x - avg) / cnt
+            ge = gv[r].to(dtype) * 2.0 * (x if variant == 'no_avg' else x - avg) / cnt
             me = gv[r].abs() * (2.0 / cnt) * (A + Aavg)
             for w, idx, ok in tp:
-                g64[src].index_add_(1, idx, w[None] * ge)
+                g[src].index_add_(1, idx, w[None].to(dtype) * ge)
                 M[src].index_add_(1, idx, w[None] * me)
                 N[src].index_add_(0, idx, ok.double())
     shape = (n_img, C, Hf, Wf)
-    return dict(g64=g64.reshape(shape), M=M.reshape(shape), N=N[:, None].expand(n_img, C, Hf * Wf).reshape(shape).clone(),
+    return dict(g64=g.reshape(shape), M=M.reshape(shape), N=N[:, None].expand(n_img, C, Hf * Wf).reshape(shape).clone(),
                 cnt_max=cnt_max)
 
 
-def affected_images(case, variant):
-    """bool [n_img]: the images whose gradient a CHUNK_VARIANTS bug can change -- for 'avg_first_chunk' the sources of the
+def affected_images(case, variant, pos=None):
+    """bool [n_img]: the images whose gradient a wrong-gradient variant can change -- for 'avg_first_chunk' the sources of the
     references with more than one chunk, for 'drop_later_chunks' / 'stale_records' their sources at CSR position 8 or higher,
-    for the plane variants all sources."""
-    pos = positions(case)
+    for every other variant (the plane variants here) all sources of a reference.  ``pos``: the positions list (default: this
+    module's ``positions(case)``)."""
+    pos = positions(case) if pos is None else pos
     mask = torch.zeros(case['feat'].shape[0], dtype=torch.bool)
     for r in sorted({p[0] for p in pos}):
         srcs = [p[1] for p in pos if p[0] == r]
-        if variant in ('first_segment', 'tail_plane'):
+        if variant not in ('avg_first_chunk', 'drop_later_chunks', 'stale_records'):
             mask[srcs] = True
         elif len(srcs) > CHUNK:
             mask[srcs if variant == 'avg_first_chunk' else srcs[CHUNK:]] = True

@@ -286,6 +286,40 @@ def test_saved_state_is_not_edge_sized(cuda):
     _depth_inside(gd, case, 'depth_pred.add_() between forward and backward')
 
 
+@pytest.mark.parametrize('cam', ['rotated', 'sliding'])
+def test_plane_sweep_and_backprojection_are_one_walk(cuda, cam):
+    """The two entry points run one walk (csrc/variance_backward.h) over two sample axes.  A matched problem: pbo.make_case(32, cam)
+    with 7 planes 0.5, 0.75 .. 2.0, and the same cameras, features and edges with a constant depth map 1.25 on the 7 x 9 grid,
+    offset 0.25, n = 3 and the same gvar permuted to [n_ref * P, 7, C].  Every number is exact in binary, so the hypothesis depths
+    are the plane depths and the sample positions are bit-equal (asserted on the oracles' positions).  Each feature gradient lies
+    within pbo.bound of the ONE oracle, and the two agree within twice that bound per element: each is within the bound of the
+    same g64, and the atomics fix no order, so no bit-equality is asked for."""
+    import psv_backward_oracle as pbo
+    tr = v3d('training')
+    pc = pbo.make_case(32, cam)
+    pc = dict(pc, depth=(0.5, 0.25, 7), gvar=pc['gvar'][:, :, :7].contiguous())
+    n_ref, C, D, h, w = pc['gvar'].shape
+    bc = dict(pc, depth_map=torch.full((n_ref, h, w), 1.25), offset=0.25, n=3,
+              gvar=pc['gvar'].permute(0, 3, 4, 2, 1).reshape(n_ref * h * w, D, C).contiguous())
+    for (rp, sp, xp, yp), (rb, sb, xb, yb) in zip(pbo.positions(pc), bbo.positions(bc)):
+        assert (rp, sp) == (rb, sb)
+        for a, b in ((xp, xb), (yp, yb)):
+            assert torch.equal(a.view(D, h * w).t().reshape(-1).view(torch.int32), b.view(torch.int32))
+    orc = pbo.gradient(pc)
+    feat = pc['feat'].to(cuda).requires_grad_(True)
+    var = tr.plane_sweep_variance(feat, pc['rotmats'], pc['tvecs'], pc['K'], pc['edges'], *pc['depth'], pc['img_size'],
+                                  pc['plane_size'])
+    g_psv = torch.autograd.grad(var, feat, grad_outputs=pc['gvar'].to(cuda))[0]
+    _, feat, _, var = _forward(bc, cuda)
+    g_bp = torch.autograd.grad(var, feat, grad_outputs=bc['gvar'].to(cuda))[0]
+    _inside(g_psv, orc, 'plane sweep, %s' % cam)
+    _inside(g_bp, orc, 'back-projection, %s' % cam)
+    diff, allowed = (g_psv.double() - g_bp.double()).abs().cpu(), 2.0 * pbo.bound(orc)
+    nz = allowed > 0
+    print('%s: worst |g_psv - g_bp| / (2 bound) = %.3f' % (cam, float((diff[nz] / allowed[nz]).max())))
+    assert float(g_psv.abs().max()) > 0 and bool((diff <= allowed).all())
+
+
 LIMITS = ['C=8', 'grad_pts with n_half=1', 'grad_var without grad_feat_cl', 'grad_feat_cl without grad_var',
           'grad_pts without grad_depth', 'grad_depth without grad_pts', 'neither pair', 'Wf=32760', 'Hf=32760', 'H=1', 'W=1']
 

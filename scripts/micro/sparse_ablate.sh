@@ -1,4 +1,4 @@
-# Developer: ablations of the sparse-convolution pipeline kernel (0 full, 1 no MFMAs, 2 no fragment loads, 3 no gathers, 4 no split /
+# Developer: ablations of the sparse-convolution pipeline kernel (csrc/gemm_sparse.hip, -DV3D_PIPE_ABLATE=a: 0 full, 1 no MFMAs, 2 no fragment loads, 3 no gathers, 4 no split /
 # LDS writes) with the phase counters of both roles (0 prologue, 1 fragment issue, 2 matrix phase, 3 barrier | loader: 4 commit incl. the
 # wait for the gathers, 5 gather issue, 6 barrier, 7 prologue)
 for a in 0 1 2 3 4; do for cfgs in "13434 128" "59975 64"; do set -- $cfgs

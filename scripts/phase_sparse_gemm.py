@@ -2,7 +2,8 @@
 """Developer tool: one sparse-convolution-shaped gather-GEMM (27 segments over one source, row maps = a synthetic neighbour
 table: rows within +-span of the output row, a fraction absent), timed; with a library built with -DV3D_PHASE_TIMING also the
 phase shares of the rounds kernel (0 row table, 1 barrier, 2 commit incl. the wait for the gathers, 3 barrier, 4 gather issue,
-5 MFMA + fragment loads, 6 epilogue).    python scripts/phase_sparse_gemm.py --rows 13500 --c 128"""
+5 MFMA + fragment loads, 6 epilogue).  The counters are per translation unit: the rounds and pipeline kernels' come from
+csrc/gemm_sparse.hip's reader, the one-step kernel's (V3D_OPTIONS=gemm_rounds=0) from csrc/gemm_dense.hip's.    python scripts/phase_sparse_gemm.py --rows 13500 --c 128"""
 import argparse, ctypes, importlib, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap = argparse.ArgumentParser()
@@ -32,8 +33,11 @@ for _ in range(10): run()
 t1.record(); torch.cuda.synchronize()
 ms = t0.elapsed_time(t1) / 10
 msg = 'M=%d C=%d: %.1f us = %.1f TFLOP/s' % (M, C, ms * 1e3, 2.0 * M * 27 * (1 - args.absent) * C * C / ms / 1e9)
-if hasattr(lib, 'v3d_debug_gemm_phase_read'):
-    fn = lib.v3d_debug_gemm_phase_read; fn.restype = ctypes.c_int; fn.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]
-    buf = (ctypes.c_ulonglong * 8)(); rows = 64 if M >= 8192 else 32; nb = (M + rows - 1) // rows; fn(buf, nb); tot = sum(buf)
+opt = {}
+for o in ('gemm_rounds', 'gemm_pipe'): opt[o] = libm.set_option(o, 1); libm.set_option(o, opt[o])      # read the options: which kernel ran?
+reader = 'v3d_debug_sparse_gemm_phase_read' if opt['gemm_rounds'] else 'v3d_debug_gemm_phase_read'
+if hasattr(lib, reader):
+    fn = getattr(lib, reader); fn.restype = ctypes.c_int; fn.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]
+    buf = (ctypes.c_ulonglong * 8)(); rows = 64 if M >= 8192 and opt['gemm_rounds'] and opt['gemm_pipe'] else 32; nb = (M + rows - 1) // rows; fn(buf, nb); tot = sum(buf)
     msg += '; cycles/workgroup %.0f: ' % (tot / nb) + ' '.join('%d:%.0f' % (i, v / nb) for i, v in enumerate(buf))
 print(msg)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """How many of the 27 kernel offsets does a 64-row tile of a sparse convolution touch, by row order?  (CPU only.)
 
-The sparse-convolution kernel (csrc/gemm_gather.hip: gemm_gather_pipe_kernel) multiplies an offset for a whole tile when ANY
+The sparse-convolution kernel (csrc/gemm_sparse.hip: gemm_gather_pipe_kernel) multiplies an offset for a whole tile when ANY
 of the tile's rows has that neighbour: with the rows in key order (torch.unique of (batch, x, y, z)) almost every offset is
 live in almost every tile -- 2.4x the algorithmic matrix work.  This script builds the three coordinate maps
 of the cfg3 bench scene with the oracle's voxelisation and reports, per level and per candidate row order, the mean number of

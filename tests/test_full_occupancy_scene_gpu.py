@@ -18,7 +18,7 @@ ops on the device for the backbone; no kernel of this library computes any part 
  2. voxelisation: integer outputs EQUAL to oracle.scene.voxelize of the kernel's points, centres to 1e-6;
  3. csrc/sparse.hip: coordinate order of the three levels and all seven neighbour tables the convolutions consume (27-offset
     table per level, two stride-2 down maps, two transposed up maps) EQUAL to `_lookup`;
- 4. PointNet (gemm_gather.hip + segment.hip) on the 200 704 x 35 input made of 1-2;
+ 4. PointNet (gemm_dense.hip + segment.hip) on the 200 704 x 35 input made of 1-2;
  5. single sparse convolutions on the three real coordinate maps, seeded random features (no ReLU zeros to hide a row), through
     the entry the U-Net uses (v3d_sparse_conv_f32): one layer deep, so one wrong row cannot be averaged away by a GroupNorm;
  6. the sparse U-Net from the kernel's PointNet output;

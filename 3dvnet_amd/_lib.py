@@ -183,6 +183,9 @@ SIGNATURES = {
     'v3d_psv_variance_backward_f32': (c_int, [c_void_p] * 7 + [c_int] * 8 + [c_double] * 2 + [c_int] * 3 +
                                       [c_void_p, c_void_p, c_void_p]),
     'v3d_backproject_variance_backward_f32': (c_int, [c_void_p] * 8 + [c_int] * 10 + [c_double, c_int] + [c_void_p] * 5),
+    'v3d_sparse_conv_weight_grad_workspace_bytes': (c_size_t, [c_int] * 4),
+    'v3d_sparse_conv_weight_grad_f32': (c_int, [c_void_p, c_int, c_void_p, ctypes.c_longlong, c_int, c_void_p, c_int, c_int, c_int,
+                                                c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 

@@ -42,7 +42,7 @@ namespace {
 struct OptDef { const char* name; int def; };
 const OptDef kOptDefs[v3d::kOptCount] = {{"psv_kernel", 0}, {"c12_march", 1}, {"stop_after", 99}, {"gemm_rounds", 1},
                                          {"gemm_pipe", 1}, {"psv_walk", 0}, {"render_coop", 64},
-                                         {"psv_skip", 1}};
+                                         {"psv_skip", 1}, {"wgrad_compact", 1}};
 std::atomic<int> g_opt[v3d::kOptCount];
 std::atomic<bool> g_opt_init{false};
 void opt_init() {
@@ -66,7 +66,7 @@ extern "C" int v3d_set_option(const char* name, int value) {
   opt_init();
   for (int i = 0; i < v3d::kOptCount; ++i)
     if (!strcmp(name, kOptDefs[i].name)) {
-      V3D_REQUIRE(!(i == v3d::kOptGemmRounds || i == v3d::kOptGemmPipe || i == v3d::kOptPsvSkip) || value == 0 || value == 1, V3D_ERR_BAD_ARG,
+      V3D_REQUIRE(!(i == v3d::kOptGemmRounds || i == v3d::kOptGemmPipe || i == v3d::kOptPsvSkip || i == v3d::kOptWgradCompact) || value == 0 || value == 1, V3D_ERR_BAD_ARG,
                   "v3d_set_option: %s must be 0 or 1 (got %d)", name, value);
       V3D_REQUIRE(!(i == v3d::kOptPsvWalk || i == v3d::kOptRenderCoop) || value >= 0, V3D_ERR_BAD_ARG,
                   "v3d_set_option: %s must be >= 0 (got %d)", name, value);

@@ -23,7 +23,9 @@
 //                      fragments straight into registers) and gemm_gather_pipe_kernel (loader waves + matrix waves, one
 //                      barrier per round; the default for a convolution with a neighbour table)
 //   gemm_conv1d.hip    conv1d_gemm_kernel: the three taps of the hypothesis decoder's conv1d share one staged tile per K chunk
-// The four kernels take the steps and multiply in the same order per accumulator and share the epilogue: where more than one
+//   gemm_wgrad.hip     sparse_conv_wgrad_kernel: the weight gradient of a sparse convolution (training): the contraction runs over the
+//                      ROWS of a neighbour-table column, exact fp32, partial tiles per row chunk; its own entry point and host side
+// The four forward kernels take the steps and multiply in the same order per accumulator and share the epilogue: where more than one
 // serves a call their outputs agree bit for bit (tests/test_parity_net_gpu.py).
 #include <cstdlib>
 #include <vector>

@@ -56,6 +56,7 @@ enum Option {
   kOptPsvWalk,         // "psv_walk": plane chunks a wave of the window kernel walks: 0 auto (by shape), N = N chunks (bit-identical)
   kOptRenderCoop,      // "render_coop": bounding boxes of more than this many pixels are rasterised by the whole wave (bit-identical)
   kOptPsvSkip,         // "psv_skip": 1 the window kernel skips passes whose samples all miss the source image, 0 never (bit-identical)
+  kOptWgradCompact,    // "wgrad_compact": 1 the sparse convolution's weight-gradient kernel stages the present rows of a chunk only, 0 every row
   kOptCount
 };
 int option(Option o);

@@ -1,5 +1,6 @@
-"""Training of the cost-volume stage (stage 1) and of the entry of stage 2: the pieces of ``mv3d/subnetworks/mvsnet.py:186-227``,
-of the initial depth supervision (``mv3d/lightningmodel.py:57-63``) and of the back-projected variance with a backward pass.
+"""Training of the cost-volume stage (stage 1), of the entry of stage 2, of the hypothesis decoder and of the sparse U-Net: the pieces
+of ``mv3d/subnetworks/mvsnet.py:186-227``, of the initial depth supervision (``mv3d/lightningmodel.py:57-63``), of the
+back-projected variance, of ``run_pointflow`` and of ``SparseUNet.forward`` with a backward pass.
 
 Only one operation of stage 1 has no stock-torch route that is usable on the device: the fused warp + variance (rows
 A1-A4).  Its backward is ``csrc/psv_backward.hip`` behind ``v3d_psv_variance_backward_f32`` (include/v3d.h); like the forward
@@ -29,10 +30,21 @@ inverted index of the forward's corner table, without atomics, bitwise reproduci
   * ``hypothesis_decoder``                               Conv1d / BatchNorm1d / ReLU stack, head and softmax, functional;
   * ``pointflow_offset``                                 hypotheses -> features -> decoder -> expected offset of ``run_pointflow``.
 
+The producer of those level features is the sparse U-Net (``mv3d/subnetworks/scenemodeling.py:147-237``).  Its convolutions have
+no usable stock route either: 27 ``index_select`` + ``matmul`` pairs per convolution whose gathered copies autograd keeps.  The
+input gradient of a convolution is the forward gather-GEMM (``v3d_sparse_conv_f32``) on the output gradient over the INVERSE
+neighbour table with every slab transposed; the weight gradient is ``v3d_sparse_conv_weight_grad_f32`` (``csrc/gemm_wgrad.hip``):
+exact-fp32 matrix instructions, partial tiles per row chunk added in chunk order, no atomics, bitwise reproducible.
+GroupNorm, ReLU, the residual add and the 1x1 ``feat_adj`` are stock differentiable torch ops over the existing parameters:
+
+  * ``SparseConv`` / ``sparse_conv``                     one convolution (no norm, residual or ReLU) -> x and kernel gradients;
+  * ``sparse_unet``                                      ``SparseUNet.forward`` -> the level features, differentiable in the
+                                                         input F and in every U-Net parameter; plugs into ``pointflow_offset``.
+
 Cameras, plane depths, offsets and edges are data (no gradient), as in the reference, which also builds every sampling grid under
 ``no_grad``.  The image-feature gradients are summed with fp32 atomic adds: their last bits can differ from call to call (DESIGN.md
-4.1b, 4.1c).  Out of scope: the rest of stage 2 (PointNet and the sparse U-Net: they connect to the level-feature gradients
-produced here), stage 3, the native backbone, the split / channel-last variance formats, ``PL3DVNet.forward`` in training mode,
+4.1b, 4.1c).  Out of scope: the rest of stage 2 (PointNet and the voxel pooling: they connect to the gradient of F produced
+here), stage 3, the native backbone, the split / channel-last variance formats, ``PL3DVNet.forward`` in training mode,
 an optimiser loop.  No CPU fallback.
 """
 import torch
@@ -326,6 +338,158 @@ def pointflow_offset(decoder, xs, depth_pred, depth_batch, img_feats, rotmats, t
     preds = hypothesis_decoder(decoder, features, bn_training=bn_training)
     offset_vals = torch.linspace(-n * offset, n * offset, 2 * n + 1).to(preds)       # on the CPU, then moved (:238-240)
     return torch.sum(offset_vals.unsqueeze(0) * preds, dim=1).view(depth_pred.shape)
+
+
+def _row_matrix(t, C):
+    """A [rows, C] gradient as the C ABI takes it -> (tensor, row stride).  The backward of `cat` hands out a view of a wider row:
+    its own row stride is passed on when 16-byte loads can read it; anything else (a stride-0 expanded tensor of a .sum(), a
+    transposed view, another dtype) becomes one contiguous fp32 copy."""
+    st = t.stride()
+    if not (t.dtype == torch.float32 and t.shape[0] > 0 and st[1] == 1 and st[0] >= C and st[0] % 4 == 0 and t.data_ptr() % 16 == 0):
+        t = t.float().contiguous()
+        return t, C
+    return t, st[0]
+
+
+def _gather_gemm(src, ld, kernel, nbr, n_rows, transposed, n_calls, precision):
+    """``v3d_sparse_conv_f32`` (``use_gn = 0``, ``relu_out = 0``, no residual) over the offsets of ``nbr`` [n_seg, >= n_rows] ->
+    [n_rows, Co] (``transposed``: every slab transposed -> [n_rows, Ci]).  ``n_calls`` > 1: one call per group of n_seg / n_calls
+    consecutive offsets, the partial results added pairwise (shorter accumulation chains, see ``SparseConv``)."""
+    from .scenemodeling import PackedGemm
+    lib = _lib.load()
+    dev = src.device
+    n_seg, ci, co = kernel.shape
+    per = n_seg // n_calls
+    N, K = (ci, co) if transposed else (co, ci)
+    outs = []
+    with torch.cuda.device(dev):
+        for j in range(n_calls):
+            # slab k addressed as w[k][n][kk]: [Ci, Co] read as (n = co, kk = ci), transposed as (n = ci, kk = co)
+            pack = PackedGemm(kernel.detach()[j * per:(j + 1) * per], ci * co, co if transposed else 1, 1 if transposed else co, per,
+                              N, K, device=dev)                                              # no GroupNorm affine
+            y = torch.empty((n_rows, N), dtype=torch.float32, device=dev)
+            rc = lib.v3d_sparse_conv_f32(pack.handle, n_rows, src.data_ptr(), ld, nbr[j * per:].data_ptr(), nbr.shape[1], 0, 0.0, None,
+                                         0, 0, _lib.ptr(y), N, _lib.precision_code(precision), _lib.stream_ptr(dev))
+            _lib.check(rc, 'v3d_sparse_conv_f32')
+            outs.append(y)
+    while len(outs) > 1:
+        outs = [outs[i] + outs[i + 1] if i + 1 < len(outs) else outs[i] for i in range(0, len(outs), 2)]
+    return outs[0]
+
+
+class SparseConv(torch.autograd.Function):
+    """A sparse convolution without norm, residual or ReLU -- ``v3d_sparse_conv_f32`` with ``use_gn = 0``, ``relu_out = 0`` -- with
+    both gradients.  ``nbr`` [27, n_out] is the forward's table A.neighbors(B.coords, step), ``nbr_inv`` [27, n_in]
+    its inverse B.neighbors(A.coords, -step).  To ``x``: the same call on ``grad_out`` over ``nbr_inv`` with every slab transposed
+    (the same offset index).  To ``kernel``: ``v3d_sparse_conv_weight_grad_f32`` (exact fp32 in both precisions, no atomics,
+    bitwise reproducible).  The node saves ``x``, ``kernel`` and the two tables: nothing of size 27 * M * C.
+
+    Precision ``'fp32'`` runs the FORWARD as nine calls of three offsets each and adds the nine partial results pairwise.  The
+    exact-fp32 kernel adds the 27 * Ci products of an output into one accumulator in sequence; GroupNorm's backward reads the
+    forward values, and with one 27-offset call the gradients of the whole U-Net were about twice as far from float64 as those of a
+    stock float32 graph (up to 4.8 times on single gradients); with chains of 3 * Ci they are as close.  The
+    default ``'split_bf16'``, whose products carry 2^-16 each, is one call: the bits of the inference forward."""
+    FP32_FORWARD_CALLS = 9
+
+    @staticmethod
+    def forward(ctx, x, kernel, nbr, nbr_inv, precision):
+        n_seg, ci, co = kernel.shape
+        n_out = nbr.shape[1]
+        assert x.dim() == 2 and x.shape[1] == ci and nbr.shape[0] == n_seg and nbr_inv.shape == (n_seg, x.shape[0])
+        assert nbr.dtype == torch.int32 and nbr_inv.dtype == torch.int32
+        xc = x.detach().float().contiguous()
+        n_calls = SparseConv.FP32_FORWARD_CALLS if precision == 'fp32' and n_seg % SparseConv.FP32_FORWARD_CALLS == 0 else 1
+        y = _gather_gemm(xc, ci, kernel, nbr, n_out, False, n_calls, precision)
+        ctx.save_for_backward(x, kernel, nbr, nbr_inv)
+        ctx.precision = precision
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        x, kernel, nbr, nbr_inv = ctx.saved_tensors
+        lib = _lib.load()
+        dev = x.device
+        n_seg, ci, co = kernel.shape
+        n_in, n_out = x.shape[0], nbr.shape[1]
+        assert grad_out.shape == (n_out, co)
+        g, ld_g = _row_matrix(grad_out, co)
+        grad_x = grad_w = None
+        if ctx.needs_input_grad[0]:
+            # dx[a] = sum_k g[nbr_inv[k, a]] @ kernel[k]^T
+            grad_x = _gather_gemm(g, ld_g, kernel, nbr_inv, n_in, True, 1, ctx.precision).to(x.dtype)
+        with torch.cuda.device(dev):
+            if ctx.needs_input_grad[1]:
+                xc = x.detach().float().contiguous()
+                grad_w = torch.empty((n_seg, ci, co), dtype=torch.float32, device=dev)      # every element is written
+                nbytes = lib.v3d_sparse_conv_weight_grad_workspace_bytes(n_out, n_seg, ci, co)
+                ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+                rc = lib.v3d_sparse_conv_weight_grad_f32(_lib.ptr(xc), ci, _lib.ptr(nbr), nbr.shape[1], n_seg, g.data_ptr(), ld_g, n_out,
+                                                         ci, co, _lib.ptr(grad_w), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+                _lib.check(rc, 'v3d_sparse_conv_weight_grad_f32')
+                grad_w = grad_w.to(kernel.dtype)
+        return grad_x, grad_w, None, None, None
+
+
+def sparse_conv(x, kernel, nbr, nbr_inv, precision='split_bf16'):
+    """y[p] = sum_k [nbr[k, p] >= 0] x[nbr[k, p]] @ kernel[k] as a differentiable function of ``x`` [n_in, Ci] and ``kernel``
+    [27, Ci, Co] (Ci, Co multiples of 16 up to 128); ``nbr`` [27, n_out] / ``nbr_inv`` [27, n_in] int32 as in ``SparseConv``."""
+    mvsnet._require_cuda(x, 'training.sparse_conv')
+    mvsnet._require_cuda(kernel, 'training.sparse_conv')
+    _lib.precision_code(precision)
+    return SparseConv.apply(x, kernel, nbr.contiguous(), nbr_inv.contiguous(), precision)
+
+
+def _group_norm(norm, y):
+    gn = norm.gn                                                # MinkowskiGroupNorm: gn(input.F), every voxel row on its own
+    return F.group_norm(y, gn.num_groups, gn.weight, gn.bias, gn.eps)
+
+
+def sparse_unet(unet, feats, xs):
+    """``SparseUNet.forward`` (scenemodeling.py:147-237) as a differentiable function -> ``level_feats``: one [N_l, C_l] tensor
+    per level in the order of ``xs`` (coarse to fine), differentiable in ``feats`` [N, C_0] and in every parameter of ``unet``
+    (kernels, GroupNorm weights and biases, ``feat_adj``; no second parameter set, ``state_dict`` keys untouched).  ``xs``: the
+    result of the inference call ``unet(feats, pts, idx, batch, res)`` on the same input; its ``x['sparse']`` supply every
+    coordinate map and hash table.  Convolutions are ``sparse_conv`` in ``unet.precision``; GroupNorm, ReLU, the residual add and
+    the 1x1 ``feat_adj`` are stock torch ops.  The result plugs into ``pointflow_offset(..., level_feats=...)``."""
+    mvsnet._require_cuda(feats, 'training.sparse_unet')
+    prec = unet.precision
+    n_lv = len(unet.dims)
+    assert len(xs) == n_lv
+    levels = [x['sparse'] for x in xs][::-1]                    # fine to coarse, as SparseUNet.forward builds them
+    assert feats.shape[0] == levels[0].n
+    # each same-level table once per level; its inverse is the table with the 27 rows reversed (o_{26 - k} = -o_k)
+    same = [lv.neighbors(lv.coords, lv.stride) for lv in levels]
+    same_inv = [t.flip(0).contiguous() for t in same]
+    # down table of level i (rows of level i - 1) and up table back (rows of level i): each other's inverse
+    down = [None] + [levels[i - 1].neighbors(levels[i].coords, levels[i - 1].stride) for i in range(1, n_lv)]
+    up = [None] + [levels[i].neighbors(levels[i - 1].coords, -levels[i - 1].stride) for i in range(1, n_lv)]
+
+    def conv_gn_relu(seq, x, nbr, inv):
+        return F.relu(_group_norm(seq[1], sparse_conv(x, seq[0].kernel, nbr, inv, prec)))
+
+    def residual(blk, x, i):
+        y = F.relu(_group_norm(blk.n1, sparse_conv(x, blk.conv1.kernel, same[i], same_inv[i], prec)))
+        return F.relu(_group_norm(blk.n2, sparse_conv(y, blk.conv2.kernel, same[i], same_inv[i], prec)) + x)
+
+    x = feats.float()
+    skips = []
+    for i in range(n_lv):
+        if i > 0:
+            x = conv_gn_relu(unet.down[i - 1], x, down[i], up[i])                       # stride-2 conv
+        for blk in unet.res_down[i]:
+            x = residual(blk, x, i)
+        skips.append(x)
+    out = [x]
+    for j in range(n_lv - 1):
+        i = n_lv - 1 - j                                                                 # from level i up to level i - 1
+        u = conv_gn_relu(unet.up[j], x, up[i], down[i])                                  # transposed conv
+        adj = unet.feat_adj[j]
+        x = F.relu(_group_norm(adj[1], torch.cat((u, skips[i - 1]), dim=1) @ adj[0].kernel))      # 1x1 on ME.cat
+        for blk in unet.res_up[j]:
+            x = residual(blk, x, i - 1)
+        out.append(x)
+    return out
 
 
 def _conv_bn_relu(mod, x, bn_training):

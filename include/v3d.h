@@ -77,8 +77,8 @@ extern "C" {
  *                                smaller ones by the triangle's own thread (default 64; 0 = every box; bit-identical)
  *   "psv_skip"        1 | 0      the window warp kernel skips an (edge, 8 planes, 8 pixels) pass whose samples all fall beside the
  *                                source image (they add exactly zero) | never skips (bit-identical)
- * Unknown names, gemm_rounds / gemm_pipe / psv_skip values other than 0 and 1, and a negative psv_walk / render_coop -> V3D_ERR_BAD_ARG.
- * ("psv_walk", "render_coop" and "psv_skip" are additive within ABI version 9: new option names, no changed signature; v3d_version() is not
+ * Unknown names, gemm_rounds / gemm_pipe / psv_skip / wgrad_compact values other than 0 and 1, and a negative psv_walk / render_coop -> V3D_ERR_BAD_ARG.
+ * ("psv_walk", "render_coop", "psv_skip" and "wgrad_compact" are additive within ABI version 9: new option names, no changed signature; v3d_version() is not
  * bumped.) */
 int v3d_set_option(const char* name, int value);
 int v3d_get_option(const char* name, int* value);
@@ -337,6 +337,25 @@ int v3d_gemm_gather_f32(const v3d_gemm_weights* handle, int M, const float* cons
 int v3d_sparse_conv_f32(const v3d_gemm_weights* handle, int M, const float* src, int ld_src, const int32_t* nbr,
                         long long nbr_stride, int use_gn, float gn_eps, const float* residual, int ld_res, int relu_out,
                         float* out, int ld_out, int precision, void* stream);
+/* The weight gradient of that convolution (training; additive within ABI version 9):
+ *   grad_w[k, ci, co] = sum over the rows p < M with nbr[k * nbr_stride + p] >= 0 of src[nbr[k, p] * ld_src + ci] * grad_out[p * ld_grad + co]
+ * for the forward's table `nbr` ([n_seg, nbr_stride] int32, entries in [-1, n_in): the caller's contract, not checked), its source
+ * `src` [n_in, ld_src] (first K columns) and the gradient `grad_out` [M, ld_grad] (first N columns) of its M output rows.
+ * grad_w [n_seg, K, N] contiguous (the layout of _SparseConv.kernel): EVERY element is written; a slab whose offset has no present
+ * row is exactly 0, and so is everything with M == 0 (src, nbr, grad_out and workspace may then be null).  Exact-fp32 matrix
+ * instructions, no float atomics: the row chunks are a function of M alone (512-row blocks, at most 128 chunks), a chunk's partial
+ * tile goes to the workspace and the partials are added in chunk order -- two calls return the same bits, on any device.  Source
+ * rows no table entry names and columns behind K / N are never read.  No step synchronises with the host.
+ * Errors, all before anything is enqueued and with grad_w untouched: V3D_ERR_BAD_SHAPE unless 0 <= M <= 2^30, 1 <= n_seg <= 27, K and N
+ * multiples of 16 in [16, 128], ld_src >= K, ld_grad >= N, nbr_stride >= M; V3D_ERR_BAD_ARG for a null pointer, a src / grad_out /
+ * grad_w / workspace that is not 16-byte aligned or an ld that is no multiple of 4; V3D_ERR_WORKSPACE_TOO_SMALL.
+ * v3d_sparse_conv_weight_grad_workspace_bytes returns 0 for a shape the call refuses (and for M == 0).
+ * Developer option "wgrad_compact" (v3d_set_option; 1 | 0, default 1): the kernel stages the present rows of a row chunk only | every
+ * row, absent ones as zero rows (the same terms; the groups of four rows the matrix instruction adds differ). */
+size_t v3d_sparse_conv_weight_grad_workspace_bytes(int M, int n_seg, int K, int N);
+int v3d_sparse_conv_weight_grad_f32(const float* src, int ld_src, const int32_t* nbr, long long nbr_stride, int n_seg,
+                                    const float* grad_out, int ld_grad, int M, int K, int N, float* grad_w, void* workspace,
+                                    size_t workspace_bytes, void* stream);
 int v3d_fill_f32(float* ptr, size_t n, float value, void* stream);
 /* PointNet input of PL3DVNet.model_scene (mv3d/lightningmodel.py:180-183): out[i] = [pts[edge_pt[i]] - anchor_pts[edge_anchor[i]]
  * | pts_feat[edge_pt[i]]], out [n_edges, 3 + C]; pts [*, 3], anchor_pts [*, 3], pts_feat [*, C], edges int64. */

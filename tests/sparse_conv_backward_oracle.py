@@ -18,6 +18,26 @@ Bound of the weight gradient, per element: with cnt_k the present rows of offset
 
 cnt_k - 1 additions in any order are (cnt_k - 1) u S to first order; the 32 are tests/psv_backward_oracle.py's constant and hold the
 product roundings, the additions of the chunk partials and the matrix instruction's internal order.  S = 0 demands exact zero.
+
+Bound of the input gradient (`input_grad_bound`), and of the forward with (x, nbr) in place of (g, inv): per element, with
+n = (present offsets of the row) x (contracted width) and S = sum |g| |w| over the same terms,
+
+  'fp32'         |dx_kernel - dx_64| <= (n + 32) u S                     the same constant: n - 1 additions in any order
+  'split_bf16'   |dx_kernel - dx_64| <= (2^-16 + (n + 32) u) S
+
+The 2^-16 comes from csrc/bf16_split.h, not from a measurement: an operand a is carried as hi + lo with hi = RNE_bf16(a) and
+lo = RNE_bf16(a - hi); the kernel forms hi hi' + hi lo' + lo hi' and drops lo lo'.  A product is off by the residual a - hi - lo of
+either operand and by the dropped term: three terms.  With the mean rounding error of 8 significant bits, 2^-9 |a| per rounding,
+each of the three is 2^-18 |a a'| and their sum is below 2^-16 |a a'|: that is the constant.  It is NOT the worst case of one
+product: half an ulp of bf16 at the bottom of a binade is 2^-8 |a|, so a single operand can keep a residual of 2^-16 |a| and a single
+product can be off by 3 * 2^-16 |a a'| (tests/test_sparse_conv_backward_oracle.py meets such operands in random data).  The bound
+is on a sum over n >= 16 products whose residuals are independent in size and sign; the three-product split evaluated in float64 on
+a 66 597-voxel map stays at 0.10 of it.  The bf16 products are exact in the fp32 accumulator and their additions are the
+(n + 32) u S of the fp32 mode.  S = 0 demands exact zero.
+
+`synthetic_table` builds tables without a coordinate map: the header makes entries in [-1, n_in) the caller's contract, so any such
+table is legal, and the patterns put the present rows where the compaction of the weight-gradient kernel (two ballots per wave,
+a prefix over eight wave counts, tiles of 32 present rows, blocks of 512 table entries) has its edges.
 """
 import numpy as np
 
@@ -37,6 +57,43 @@ def chunks(M):
     return (-(-nblk // per) if per else 0), per * ROWS
 
 
+def _spread(q):
+    """q = p % ROWS -> a permutation of [0, ROWS) (107 is odd; 107 * 67 = 1 mod 512): `_spread(q) < c` names the c rows 67 j mod 512,
+    j < c, which for c >= 8 lie in every wave of both halves."""
+    return (q * 107) % ROWS
+
+
+# which rows p are present, as a rule on q = p % ROWS and b = p // ROWS (M: the number of rows)
+PATTERNS = {
+    'every':      lambda p, q, b, M: np.ones_like(p, dtype=bool),
+    'none':       lambda p, q, b, M: np.zeros_like(p, dtype=bool),
+    'first':      lambda p, q, b, M: p == 0,
+    'last':       lambda p, q, b, M: p == M - 1,
+    'wave0':      lambda p, q, b, M: q < 64,                                  # one wave of the first half ...
+    'wave3':      lambda p, q, b, M: (q >= 192) & (q < 256),
+    'wave4':      lambda p, q, b, M: (q >= 256) & (q < 320),                  # ... and of the second
+    'wave7':      lambda p, q, b, M: q >= 448,
+    'odd_blocks': lambda p, q, b, M: b % 2 == 1,                              # empty blocks between full ones
+    'tile_edge':  lambda p, q, b, M: _spread(q) < 31 + b % 3,                 # 31, 32, 33 present rows in consecutive blocks
+}
+ALL_PATTERNS = tuple(PATTERNS) + ('half',)
+
+
+def synthetic_table(M, n_in, patterns, seed):
+    """A neighbour table without a coordinate map -> int64 [len(patterns), M], entries in [-1, n_in).  Row k holds the rows of
+    `patterns[k]` (a key of PATTERNS, or 'half': a seeded random half); its present rows map to DISTINCT source rows through a
+    seeded permutation of its own (injective per offset, as a real table is), so a gather of the wrong row changes the sum."""
+    assert n_in >= M
+    rng = np.random.default_rng(seed)
+    p = np.arange(M, dtype=np.int64)
+    nbr = np.full((len(patterns), M), -1, dtype=np.int64)
+    for k, name in enumerate(patterns):
+        present = rng.random(M) < 0.5 if name == 'half' else PATTERNS[name](p, p % ROWS, p // ROWS, M)
+        rows = rng.permutation(n_in)[:M]
+        nbr[k, present] = rows[present]
+    return nbr
+
+
 def occupancy_map(n, side, seed, lattice=1):
     """n voxels of a two-batch side^3 grid (coordinates from -2 on, times `lattice`), in lexicographic order.  -> int64 [n, 4]"""
     rng = np.random.default_rng(seed)
@@ -44,6 +101,23 @@ def occupancy_map(n, side, seed, lattice=1):
     c = g[np.sort(rng.choice(g.shape[0], n, replace=False))].astype(np.int64)
     c[:, 1:] = (c[:, 1:] - 2) * lattice
     return c
+
+
+_tables = {}
+
+
+def map_tables(kind, n, side, seed):
+    """`table(kind, occupancy_map(n, side, seed))` and the coordinates, computed once per process and read-only: the large maps take
+    seconds to build.  -> (nbr, inv, n_in, M, coords[, coarse coords])"""
+    key = (kind, n, side, seed)
+    if key not in _tables:
+        c = occupancy_map(n, side, seed)
+        res = table(kind, c) + (c,) + (() if kind == 'same' else (so.strided_coords(c, 1),))
+        for a in res:
+            if isinstance(a, np.ndarray):
+                a.setflags(write=False)
+        _tables[key] = res
+    return _tables[key]
 
 
 def table(kind, coords, ts=1):
@@ -81,15 +155,7 @@ def bound(orc):
 
 def violations(got, orc):
     """-> (elements outside the bound, worst |got - dW| / bound over S > 0, largest |got| over S == 0); a NaN is outside."""
-    got = np.asarray(got, dtype=np.float64)
-    err, b = np.abs(got - orc['dW']), bound(orc)
-    pos = orc['S'] > 0
-    bad = int((~(err <= b)).sum())
-    with np.errstate(invalid='ignore', divide='ignore'):
-        ratio = np.where(pos, err / np.where(pos, b, 1.0), 0.0)
-    worst = float(np.nanmax(ratio)) if pos.any() else 0.0
-    zero = np.abs(got[~pos])
-    return bad, worst, float(zero.max()) if zero.size else 0.0
+    return outside(got, orc['dW'], bound(orc))
 
 
 def input_grad(w, inv, g):
@@ -119,6 +185,41 @@ def forward(x, w, nbr):
         sel = nbr[k] >= 0
         y[sel] += x[nbr[k][sel]] @ w[k]
     return y
+
+
+def term_sums(w, inv, g, forward=False):
+    """-> (n int64 [rows, 1], S float64 [rows, width out]) of dx = input_grad(w, inv, g) (forward=True: of y = forward(x, w, nbr) with
+    (x, nbr) passed as (g, inv)): n = present offsets of the row x contracted width, S = sum |g| |w| over the same terms."""
+    w, g = np.abs(np.asarray(w, dtype=np.float64)), np.abs(np.asarray(g, dtype=np.float64))
+    width = w.shape[1] if forward else w.shape[2]                             # the contracted width
+    S = np.zeros((inv.shape[1], w.shape[2] if forward else w.shape[1]))
+    for k in range(inv.shape[0]):
+        sel = inv[k] >= 0
+        S[sel] += g[inv[k][sel]] @ (w[k] if forward else w[k].T)
+    return (inv >= 0).sum(axis=0)[:, None] * width, S
+
+
+def input_grad_bound(w, inv, g, precision, forward=False, sums=None):
+    """Per-element bound of dx = input_grad(w, inv, g) [n_in, K] for a kernel in `precision` ('fp32' or 'split_bf16'; the module
+    docstring derives both).  forward=True: of y = forward(x, w, nbr) [M, N] with (x, nbr) passed as (g, inv).  `sums`: the result
+    of term_sums on the same arguments, where it is at hand.  -> float64 array of the result's shape; 0 where no term is present
+    (S = 0: exact zero is demanded)."""
+    n, S = term_sums(w, inv, g, forward) if sums is None else sums
+    rel = {'fp32': 0.0, 'split_bf16': 2.0 ** -16}[precision]
+    return (rel + (n + C_BOUND) * U) * S
+
+
+def outside(got, ref, bnd):
+    """-> (elements outside the bound, worst |got - ref| / bound over bound > 0, largest |got| over bound == 0); a NaN is outside."""
+    got = np.asarray(got, dtype=np.float64)
+    err = np.abs(got - ref)
+    pos = bnd > 0
+    bad = int((~(err <= bnd)).sum())
+    with np.errstate(invalid='ignore', divide='ignore'):
+        ratio = np.where(pos, err / np.where(pos, bnd, 1.0), 0.0)
+    worst = float(np.nanmax(ratio)) if pos.any() else 0.0
+    zero = np.abs(got[~pos])
+    return bad, worst, float(zero.max()) if zero.size else 0.0
 
 
 def make_case(nbr, n_in, K, N, seed, pad_src=0, pad_grad=0, poison=np.nan):

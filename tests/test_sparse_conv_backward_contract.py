@@ -1,13 +1,9 @@
 """The workspace and output contract of v3d_sparse_conv_weight_grad_f32 (include/v3d.h) through the C ABI on caller-made buffers, as
 a `Case` of the table of tests/workspace_cases.py.
 
-The case is written here and REGISTERED in that table when this module is imported (`register()` below: one `CASES.append`, one
-`SIZED_BY` key), exactly as tests/test_sparse_interp_backward_contract.py does it, because this change adds test files only.  pytest
-imports every test module before it runs one, and this file's name sorts before test_workspace_cases.py and
-test_workspace_contract_gpu.py, so in a run of the suite their completeness check, their per-case checks and their GPU
-parametrisation all see the case.  Run alone, test_workspace_cases.py reports the two new entry points as missing: that is the
-table's guard doing its work, and the cure is to move `CASE` into workspace_cases.py.  The tests below hold the case to the same four
-properties with that file's own arena and helpers, so that this file also stands alone:
+The case lives in that table (`CASE` below is the table's entry), so tests/test_workspace_cases.py and
+tests/test_workspace_contract_gpu.py see it however they are run.  The tests below hold the case to the same four properties with that
+file's own arena and helpers, so that this file also stands alone:
 
   CPU   the case's inputs are seeded and built without a device; every launch of the small input has at least two workgroups, the
         last one ragged; big is at least twice small in every buffer section or in every launch; the launch lines and the chunk
@@ -24,68 +20,22 @@ import os
 
 import numpy as np
 import pytest
-import torch
 
 import sparse_conv_backward_oracle as sco
 import workspace_cases as wc
 from conftest import ROOT
-from workspace_cases import OK, p
 
-K, N = 32, 16
-SHAPES = {'small': (sco.ROWS + 37, 9), 'big': (3 * sco.ROWS + 90, 11)}     # (rows, side of the two-batch grid): 2 and 4 chunks
-
-
-def _make(size):
-    m, side = SHAPES[size]
-    nbr, _, n_in, _ = sco.table('same', sco.occupancy_map(m, side, 40 + m))
-    return sco.make_case(nbr, n_in, K, N, 41 + m, pad_src=12, pad_grad=8)
-
-
-def _run(lib, a, i):
-    wb = lib.v3d_sparse_conv_weight_grad_workspace_bytes(i['M'], 27, K, N)
-    ws = a.ws('weight_grad', wb)
-    src, nbr, g = a.put('src', i['src']), a.put('nbr', i['nbr']), a.put('grad_out', i['grad_out'])
-    out = a.out('grad_w', (27, K, N), torch.float32)
-    return (lib.v3d_sparse_conv_weight_grad_f32(p(src), i['ld_src'], p(nbr), i['M'], 27, p(g), i['ld_grad'], i['M'], K, N, p(out), p(ws), wb,
-                                                a.stream()),)
-
-
-def _check(i, out, status):
-    assert status == (OK,)
-    orc = sco.weight_grad(i['x'], i['nbr'].astype(np.int64), i['g'])
-    got = out['grad_w'].numpy()
-    assert np.isfinite(got).all() and (orc['S'] > 0).any()
-    bad, worst, worst_zero = sco.violations(got, orc)
-    assert bad == 0 and worst_zero == 0.0, 'grad_w: %d elements outside (cnt + 32) u S, worst ratio %.3f' % (bad, worst)
-
-
-CASE = wc.Case(
-    'sparse_conv_weight_grad', ('v3d_sparse_conv_weight_grad_f32',), _make, _run, _check,
-    bound='sparse_conv_backward_oracle.weight_grad within (cnt_k + 32) u S (tests/test_sparse_conv_weight_grad_gpu.py::test_sizes_and_channel_pairs)',
-    sections=lambda lib, i: {'weight_grad': lib.v3d_sparse_conv_weight_grad_workspace_bytes(i['M'], 27, K, N)},
-    # one workgroup per (chunk of 512 rows, offset): 27 independent batches of chunks; the reduction walks 27 K N / 4 float4
-    groups=lambda i: [('sparse_conv_wgrad_kernel', i['M'], sco.ROWS, 27),
-                      ('sparse_conv_wgrad_reduce_kernel', 27 * K * N // 4, 256)],
-    constants=(('constexpr int kWgradRows = 512;', 'gemm_wgrad.hip:23'),
-               ('kern<<<dim3((unsigned)ch.n, (unsigned)n_seg), 256', 'gemm_wgrad.hip:239'),
-               ('sparse_conv_wgrad_reduce_kernel<<<(unsigned)((slab4 + 255) / 256), 256', 'gemm_wgrad.hip:243')))
+K, N = wc.WGRAD_K, wc.WGRAD_N
+SHAPES = wc.WGRAD_SHAPES                                                   # (rows, side of the two-batch grid): 2 and 4 chunks
+CASE = next(c for c in wc.CASES if c.name == 'sparse_conv_weight_grad')
 SIZE_FUNCTION = 'v3d_sparse_conv_weight_grad_workspace_bytes'
-
-
-def register():
-    """Put the case into the table of tests/workspace_cases.py, once."""
-    if all(c.name != CASE.name for c in wc.CASES):
-        wc.CASES.append(CASE)
-        wc.SIZED_BY[SIZE_FUNCTION] = CASE.name
-
-
-register()
 
 
 # ---- CPU --------------------------------------------------------------------------------------------------------------------------
 
 def test_the_table_holds_the_case_and_needs_it():
-    assert CASE in wc.CASES and SIZE_FUNCTION in wc.SIZED_BY
+    assert CASE in wc.CASES and wc.SIZED_BY[SIZE_FUNCTION] == CASE.name and (K, N) == (32, 16)
+    assert SHAPES == {'small': (sco.ROWS + 37, 9), 'big': (3 * sco.ROWS + 90, 11)} and wc.WGRAD_ROWS == sco.ROWS
     rest = [c for c in wc.CASES if c is not CASE]
     assert {'v3d_sparse_conv_weight_grad_f32', SIZE_FUNCTION} <= set(wc.missing_entry_points(rest))
     assert not {'v3d_sparse_conv_weight_grad_f32', SIZE_FUNCTION} & set(wc.missing_entry_points(wc.CASES))

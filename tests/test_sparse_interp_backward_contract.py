@@ -2,12 +2,9 @@
 v3d_sparse_interp_backward_f32 -> v3d_hash_status through the C ABI on caller-made buffers, as a `Case` of the table of
 tests/workspace_cases.py.
 
-The case is written here and REGISTERED in that table when this module is imported (`register()` below: one `CASES.append`, one
-`SIZED_BY` key), because this change adds test files only.  pytest imports every test module before it runs one, and this file's name
-sorts before test_workspace_cases.py and test_workspace_contract_gpu.py, so in a run of the suite their completeness check, their
-per-case checks and their GPU parametrisation all see the case.  Run alone, test_workspace_cases.py reports the two new entry
-points as missing: that is the table's guard doing its work, and the cure is to move `CASE` into workspace_cases.py.  The tests
-below hold the case to the same four properties with that file's own arena and helpers, so that this file also stands alone:
+The case lives in that table (`CASE` below is the table's entry), so tests/test_workspace_cases.py and
+tests/test_workspace_contract_gpu.py see it however they are run.  The tests below hold the case to the same four properties with that
+file's own arena and helpers, so that this file also stands alone:
 
   CPU   the case's inputs are seeded and built without a device; every launch of the small input has at least two workgroups, the
         last one ragged; big is at least twice small in every buffer section or in every launch; the launch lines and the chunk
@@ -23,79 +20,20 @@ import os
 
 import numpy as np
 import pytest
-import torch
 
 import sparse_interp_backward_oracle as sbo
 import workspace_cases as wc
 from conftest import ROOT
-from workspace_cases import OK, p
 
-C = 32
-HASH = next(c for c in wc.CASES if c.name == 'hash_chain')
-
-
-def _make(size):
-    i = HASH.make(size)                                                       # the map and the queries of the forward's case
-    rng = np.random.default_rng(70 + i['n'])
-    ld, col0 = C + 12, 8
-    grad = np.full((i['n_pts'] * i['n_hyp'], ld), np.nan, dtype=np.float32)
-    grad[:, col0:col0 + C] = rng.standard_normal((grad.shape[0], C)).astype(np.float32)
-    return dict(i, grad_out=grad, ld=ld, col0=col0, C=C, ts=1)
-
-
-def _run(lib, a, i):
-    n, n_pts, n_hyp, s = i['n'], i['n_pts'], i['n_hyp'], a.stream()
-    tb, wb = lib.v3d_hash_bytes(n), lib.v3d_sparse_interp_backward_workspace_bytes(n, C, n_pts, n_hyp)
-    table, ws = a.ws('table', tb), a.ws('interp_backward', wb)
-    c = a.put('coords', i['coords'], torch.int32)
-    assert lib.v3d_hash_build(p(c), n, p(table), tb, s) == OK
-    out = a.out('grad_feats', (n, C), torch.float32)
-    g, pts, pb, mn = a.put('g', i['grad_out']), a.put('pts', i['pts']), a.put('pb', i['pts_batch']), a.put('mn', i['min_pts'])
-    assert lib.v3d_sparse_interp_backward_f32(p(table), n, C, 1, p(pts), p(pb), n_pts, n_hyp, p(mn), i['res'], p(g), i['ld'], i['col0'],
-                                              p(out), p(ws), wb, s) == OK
-    return (lib.v3d_hash_status(p(table), n, s),)
-
-
-def _check(i, out, status):
-    assert status == (OK,)
-    orc = sbo.gradient(i)
-    bad, worst, worst_zero = sbo.violations(out['grad_feats'].numpy(), orc)
-    assert (orc['S'] > 0).any()
-    assert bad == 0 and worst_zero == 0.0, 'grad_feats: %d elements outside (cnt + 2) u S, worst ratio %.3f' % (bad, worst)
-
-
-CASE = wc.Case(
-    'sparse_interp_backward', ('v3d_sparse_interp_backward_f32',), _make, _run, _check,
-    bound='sparse_interp_backward_oracle.gradient within (cnt + 2) u S (tests/test_sparse_interp_backward_gpu.py::test_every_element_within_the_bound)',
-    sections=lambda lib, i: {'table': lib.v3d_hash_bytes(i['n']),
-                             'interp_backward': lib.v3d_sparse_interp_backward_workspace_bytes(i['n'], C, i['n_pts'], i['n_hyp'])},
-    groups=lambda i: [('interp_corners / interp_backward_segment', i['n_pts'] * i['n_hyp'] * 8, 256),
-                      ('interp_backward_count_kernel', i['n'] + 1, 256),
-                      ('interp_backward_chunk_kernel', (i['n_pts'] * i['n_hyp'] * 8 // sbo.CHUNK + i['n']) * (C // 4), 256),
-                      ('interp_backward_combine_kernel', i['n'] * (C // 4), 256)],
-    constants=(('kInterpBwdChunk = 512', 'sparse.hip:200'),
-               ('interp_backward_segment_kernel<<<(unsigned)((nq * 8 + 255) / 256), 256', 'sparse.hip:368'),
-               ('interp_backward_count_kernel<<<(unsigned)(((long long)n_in + 256) / 256), 256', 'sparse.hip:374'),
-               ('interp_backward_chunk_kernel<true><<<blocks, 256', 'sparse.hip:381'),
-               ('interp_backward_combine_kernel<<<(unsigned)(((long long)n_in * tpc + 255) / 256), 256', 'sparse.hip:386')),
-    paired=True)
+C = wc.INTERP_BWD_C
+CASE = next(c for c in wc.CASES if c.name == 'sparse_interp_backward')
 SIZE_FUNCTION = 'v3d_sparse_interp_backward_workspace_bytes'
-
-
-def register():
-    """Put the case into the table of tests/workspace_cases.py, once."""
-    if all(c.name != CASE.name for c in wc.CASES):
-        wc.CASES.append(CASE)
-        wc.SIZED_BY[SIZE_FUNCTION] = CASE.name
-
-
-register()
 
 
 # ---- CPU --------------------------------------------------------------------------------------------------------------------------
 
 def test_the_table_holds_the_case_and_needs_it():
-    assert CASE in wc.CASES and wc.missing_entry_points(wc.CASES) == []
+    assert CASE in wc.CASES and wc.missing_entry_points(wc.CASES) == [] and wc.SIZED_BY[SIZE_FUNCTION] == CASE.name and C == 32
     rest = [c for c in wc.CASES if c is not CASE]
     assert set(wc.missing_entry_points(rest)) == {'v3d_sparse_interp_backward_f32', SIZE_FUNCTION}
     fns = wc.header_functions()

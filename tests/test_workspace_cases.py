@@ -70,7 +70,8 @@ def test_every_runnable_case_is_whole():
     with_status = {c.name for c in RUNNABLE if c.rejected}
     assert with_status == {'edges_csr', 'voxelize_chain', 'hash_chain', 'cloud_downsample', 'mesh_render_depth'}
     assert {c.name for c in RUNNABLE if c.paired} >= {'voxelize_chain', 'mesh_count_extract', 'hash_chain', 'edges_csr', 'cloud_downsample',
-                                                      'backproject_variance', 'segment_csr_max'}
+                                                      'backproject_variance', 'segment_csr_max', 'sparse_interp_backward'}
+    assert {'sparse_interp_backward', 'sparse_conv_weight_grad'} <= {c.name for c in RUNNABLE} - with_status
 
 
 # ---- inputs and shape rules ---------------------------------------------------------------------------------------------------------

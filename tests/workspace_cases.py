@@ -1388,6 +1388,111 @@ CASES.append(Case(
     ))
 
 
+# ---- training: v3d_hash_build -> v3d_sparse_interp_backward_f32 -> v3d_hash_status; v3d_sparse_conv_weight_grad_f32 -------------------
+# (tests/test_sparse_interp_backward_contract.py and tests/test_sparse_conv_backward_contract.py hold these two cases to the four
+# properties on their own as well)
+
+INTERP_BWD_C = 32
+
+
+def _ibwd_make(size):
+    i = _hash_make(size)                                                       # the map and the queries of the forward's case
+    rng = np.random.default_rng(70 + i['n'])
+    ld, col0 = INTERP_BWD_C + 12, 8
+    grad = np.full((i['n_pts'] * i['n_hyp'], ld), np.nan, dtype=np.float32)
+    grad[:, col0:col0 + INTERP_BWD_C] = rng.standard_normal((grad.shape[0], INTERP_BWD_C)).astype(np.float32)
+    return dict(i, grad_out=grad, ld=ld, col0=col0, C=INTERP_BWD_C, ts=1)
+
+
+def _ibwd_run(lib, a, i):
+    n, n_pts, n_hyp, s, C = i['n'], i['n_pts'], i['n_hyp'], a.stream(), INTERP_BWD_C
+    tb, wb = lib.v3d_hash_bytes(n), lib.v3d_sparse_interp_backward_workspace_bytes(n, C, n_pts, n_hyp)
+    table, ws = a.ws('table', tb), a.ws('interp_backward', wb)
+    c = a.put('coords', i['coords'], torch.int32)
+    assert lib.v3d_hash_build(p(c), n, p(table), tb, s) == OK
+    out = a.out('grad_feats', (n, C), torch.float32)
+    g, pts, pb, mn = a.put('g', i['grad_out']), a.put('pts', i['pts']), a.put('pb', i['pts_batch']), a.put('mn', i['min_pts'])
+    assert lib.v3d_sparse_interp_backward_f32(p(table), n, C, 1, p(pts), p(pb), n_pts, n_hyp, p(mn), i['res'], p(g), i['ld'], i['col0'],
+                                              p(out), p(ws), wb, s) == OK
+    return (lib.v3d_hash_status(p(table), n, s),)
+
+
+def _ibwd_check(i, out, status):
+    import sparse_interp_backward_oracle as sbo
+    assert status == (OK,)
+    orc = sbo.gradient(i)
+    bad, worst, worst_zero = sbo.violations(out['grad_feats'].numpy(), orc)
+    assert (orc['S'] > 0).any()
+    assert bad == 0 and worst_zero == 0.0, 'grad_feats: %d elements outside (cnt + 2) u S, worst ratio %.3f' % (bad, worst)
+
+
+def _ibwd_groups(i):
+    import sparse_interp_backward_oracle as sbo
+    C = INTERP_BWD_C
+    return [('interp_corners / interp_backward_segment', i['n_pts'] * i['n_hyp'] * 8, 256),
+            ('interp_backward_count_kernel', i['n'] + 1, 256),
+            ('interp_backward_chunk_kernel', (i['n_pts'] * i['n_hyp'] * 8 // sbo.CHUNK + i['n']) * (C // 4), 256),
+            ('interp_backward_combine_kernel', i['n'] * (C // 4), 256)]
+
+
+CASES.append(Case(
+    'sparse_interp_backward', ('v3d_sparse_interp_backward_f32',), _ibwd_make, _ibwd_run, _ibwd_check,
+    bound='sparse_interp_backward_oracle.gradient within (cnt + 2) u S (tests/test_sparse_interp_backward_gpu.py::test_every_element_within_the_bound)',
+    sections=lambda lib, i: {'table': lib.v3d_hash_bytes(i['n']),
+                             'interp_backward': lib.v3d_sparse_interp_backward_workspace_bytes(i['n'], INTERP_BWD_C, i['n_pts'], i['n_hyp'])},
+    groups=_ibwd_groups,
+    constants=(('kInterpBwdChunk = 512', 'sparse.hip:200'),
+               ('interp_backward_segment_kernel<<<(unsigned)((nq * 8 + 255) / 256), 256', 'sparse.hip:368'),
+               ('interp_backward_count_kernel<<<(unsigned)(((long long)n_in + 256) / 256), 256', 'sparse.hip:374'),
+               ('interp_backward_chunk_kernel<true><<<blocks, 256', 'sparse.hip:381'),
+               ('interp_backward_combine_kernel<<<(unsigned)(((long long)n_in * tpc + 255) / 256), 256', 'sparse.hip:386')),
+    paired=True))
+
+
+WGRAD_K, WGRAD_N = 32, 16
+WGRAD_ROWS = 512                                                               # sparse_conv_backward_oracle.ROWS; gemm_wgrad.hip:23, cited below
+WGRAD_SHAPES = {'small': (WGRAD_ROWS + 37, 9), 'big': (3 * WGRAD_ROWS + 90, 11)}   # (rows, side of the two-batch grid): 2 and 4 chunks
+
+
+def _wgrad_make(size):
+    import sparse_conv_backward_oracle as sco
+    m, side = WGRAD_SHAPES[size]
+    nbr, _, n_in, _ = sco.table('same', sco.occupancy_map(m, side, 40 + m))
+    return sco.make_case(nbr, n_in, WGRAD_K, WGRAD_N, 41 + m, pad_src=12, pad_grad=8)
+
+
+def _wgrad_run(lib, a, i):
+    K, N = WGRAD_K, WGRAD_N
+    wb = lib.v3d_sparse_conv_weight_grad_workspace_bytes(i['M'], 27, K, N)
+    ws = a.ws('weight_grad', wb)
+    src, nbr, g = a.put('src', i['src']), a.put('nbr', i['nbr']), a.put('grad_out', i['grad_out'])
+    out = a.out('grad_w', (27, K, N), torch.float32)
+    return (lib.v3d_sparse_conv_weight_grad_f32(p(src), i['ld_src'], p(nbr), i['M'], 27, p(g), i['ld_grad'], i['M'], K, N, p(out), p(ws), wb,
+                                                a.stream()),)
+
+
+def _wgrad_check(i, out, status):
+    import sparse_conv_backward_oracle as sco
+    assert status == (OK,)
+    orc = sco.weight_grad(i['x'], i['nbr'].astype(np.int64), i['g'])
+    got = out['grad_w'].numpy()
+    assert np.isfinite(got).all() and (orc['S'] > 0).any()
+    bad, worst, worst_zero = sco.violations(got, orc)
+    assert bad == 0 and worst_zero == 0.0, 'grad_w: %d elements outside (cnt + 32) u S, worst ratio %.3f' % (bad, worst)
+
+
+CASES.append(Case(
+    'sparse_conv_weight_grad', ('v3d_sparse_conv_weight_grad_f32',), _wgrad_make, _wgrad_run, _wgrad_check,
+    bound='sparse_conv_backward_oracle.weight_grad within (cnt_k + 32) u S (tests/test_sparse_conv_weight_grad_gpu.py::test_sizes_and_channel_pairs)',
+    sections=lambda lib, i: {'weight_grad': lib.v3d_sparse_conv_weight_grad_workspace_bytes(i['M'], 27, WGRAD_K, WGRAD_N)},
+    # one workgroup per (chunk of 512 rows, offset): 27 independent batches of chunks; the reduction walks 27 K N / 4 float4
+    groups=lambda i: [('sparse_conv_wgrad_kernel', i['M'], WGRAD_ROWS, 27),
+                      ('sparse_conv_wgrad_reduce_kernel', 27 * WGRAD_K * WGRAD_N // 4, 256)],
+    constants=(('constexpr int kWgradRows = 512;', 'gemm_wgrad.hip:23'),
+               ('kern<<<dim3((unsigned)ch.n, (unsigned)n_seg), 256', 'gemm_wgrad.hip:239'),
+               ('sparse_conv_wgrad_reduce_kernel<<<(unsigned)((slab4 + 255) / 256), 256', 'gemm_wgrad.hip:243'))))
+
+
 # ---- entry points whose outputs are poisoned elsewhere -------------------------------------------------------------------------------------
 
 for _sym, _test in (('v3d_propagation_up_f32', 'test_E_stage3_past_4_gb_of_features'),
@@ -1407,7 +1512,9 @@ SIZED_BY = {
     'v3d_cloud_downsample_workspace_bytes': 'cloud_downsample', 'v3d_nn_workspace_bytes': 'nn_query',
     'v3d_cloud_metrics_workspace_bytes': 'cloud_metrics', 'v3d_mesh_workspace_bytes': 'mesh_count_extract',
     'v3d_depth_metrics_workspace_bytes': 'depth_metrics_2d', 'v3d_depth_supervision_workspace_bytes': 'depth_supervision',
-    'v3d_order_stats_workspace_bytes': 'cloud_order_stats'}
+    'v3d_order_stats_workspace_bytes': 'cloud_order_stats',
+    'v3d_sparse_interp_backward_workspace_bytes': 'sparse_interp_backward',
+    'v3d_sparse_conv_weight_grad_workspace_bytes': 'sparse_conv_weight_grad'}
 
 
 # what the issue puts in scope besides the functions with a `workspace` / `table` parameter: workspace-free calls that write whole arrays

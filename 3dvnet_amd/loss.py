@@ -1,8 +1,9 @@
 """Depth supervision on the device: the reference's ``MAELoss`` (``mv3d/loss.py:6-20``) and, in the same pass, the 2D depth metrics
 that ``PL3DVNet.forward`` takes beside it at every supervised depth map (``mv3d/lightningmodel.py:57-119``:
 ``calc_2d_depth_metrics`` without a mask against the ground truth reduced to the prediction's size).  The arithmetic is
-``csrc/supervision.hip`` behind ``v3d_depth_supervision_f32`` (include/v3d.h states the rule): one pass over the prediction, the
-ground truth gathered through the index tables of the nearest resize, no temporary.  This module is the plumbing:
+``csrc/supervision.hip`` (on ``csrc/depth2d.h``, which it shares with the 2D metrics) behind ``v3d_depth_supervision_f32``
+(include/v3d.h states the rule): one pass over the prediction, the ground truth gathered through the index tables of the nearest
+resize, no temporary.  This module is the plumbing:
 
   * ``supervise``   device tensors in, a record of device tensors out (counts, per-image rows, mean; ``mean[9]`` is the loss);
   * ``MAELoss``     the reference's module and ``forward`` signature -> the loss as a 0-dim float64 device tensor.
@@ -22,16 +23,7 @@ COUNTS = metrics2d.COUNTS + ('n_loss',)
 METRIC_KEYS = metrics2d.COLUMNS[1:]                          # calc_2d_depth_metrics without a mask, in its order
 LOSS = COLUMNS.index('loss_2d')
 Supervision = collections.namedtuple('Supervision', ('counts', 'per_image', 'mean'))
-_tables = {}
-
-
-def resize_tables(H, W, h, w, device):
-    """(row_src [h], col_src [w]) int32 on ``device``: the ground-truth row / column that
-    ``F.interpolate(gt, (h, w), mode='nearest')`` reads for every row / column of the prediction; cached."""
-    key = (H, W, h, w, str(device))
-    if key not in _tables:
-        _tables[key] = (metrics2d.nearest_index(H, h).to(device), metrics2d.nearest_index(W, w).to(device))
-    return _tables[key]
+resize_tables = metrics2d.resize_tables      # (src_h, src_w, dst_h, dst_w, device): here the source is the ground truth
 
 
 def supervise(depth_pred, depth_gt, depth_interval):

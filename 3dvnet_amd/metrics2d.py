@@ -1,7 +1,7 @@
 """2D depth metrics of predicted depth maps on the device: the reference's ``calc_2d_depth_metrics`` /
 ``calc_2d_depth_metrics_batched`` (``mv3d/eval/metricfunctions.py:6-67``) and ``process_scene_2d_metrics``
-(``mv3d/eval/processresults.py:153-169``).  The arithmetic is ``csrc/depthmetrics.hip`` behind ``v3d_depth_metrics_2d``
-(include/v3d.h states the rule): one pass over the ground truth, the predictions gathered through the index tables of the
+(``mv3d/eval/processresults.py:153-169``).  The arithmetic is ``csrc/depthmetrics.hip`` (on ``csrc/depth2d.h``, which it shares
+with the depth supervision) behind ``v3d_depth_metrics_2d`` (include/v3d.h states the rule): one pass over the ground truth, the predictions gathered through the index tables of the
 nearest resize, no temporary of the image size.  This module is the plumbing:
 
   * ``depth_metrics``                      device tensors in, a record of device tensors out (counts, per-image rows, mean);
@@ -37,11 +37,14 @@ def nearest_index(in_size, out_size):
     return F.interpolate(src, (out_size, 1), mode='nearest').view(-1).to(torch.int32)
 
 
-def resize_tables(hp, wp, H, W, device):
-    """(row_src [H], col_src [W]) int32 on ``device`` for scoring an hp x wp prediction on an H x W grid; cached."""
-    key = (hp, wp, H, W, str(device))
+def resize_tables(src_h, src_w, dst_h, dst_w, device):
+    """(row_src [dst_h], col_src [dst_w]) int32 on ``device``: the row / column of a src_h x src_w image that
+    ``F.interpolate(image, (dst_h, dst_w), mode='nearest')`` reads for every row / column of its result; cached.  The metrics
+    read an hp x wp prediction on the ground truth's H x W grid with them, the supervision (``loss.resize_tables`` is this
+    function) H x W ground truth on the prediction's h x w grid."""
+    key = (src_h, src_w, dst_h, dst_w, str(device))
     if key not in _tables:
-        _tables[key] = (nearest_index(hp, H).to(device), nearest_index(wp, W).to(device))
+        _tables[key] = (nearest_index(src_h, dst_h).to(device), nearest_index(src_w, dst_w).to(device))
     return _tables[key]
 
 

@@ -777,7 +777,7 @@ int v3d_volume_resample_nearest(const void* src, int elem_bytes, int channels, i
                                 const float* src_origin_host, const float* matrix_host, int align_corners, int nx, int ny, int nz,
                                 const float* dst_origin_host, int fill_outside, const void* fill_host, void* dst, void* stream);
 
-/* 2D depth metrics of predicted depth maps (csrc/depthmetrics.hip): mv3d/eval/metricfunctions.py:26-67 (calc_2d_depth_metrics) as
+/* 2D depth metrics of predicted depth maps (csrc/depthmetrics.hip on csrc/depth2d.h): mv3d/eval/metricfunctions.py:26-67 (calc_2d_depth_metrics) as
  * mv3d/eval/processresults.py:153-169 reaches it (nearest-enlarged predictions, valid = pred != 0 & ~isinf(pred)), in one pass
  * over the ground truth and without a temporary.  ABI version: STILL 9 -- two new symbols, nothing changed.
  *   pred [n, hp, wp] fp32; gt [n, H, W] of gt_type 0 (uint16 millimetres), 1 (fp32 metres) or 2 (fp64 metres), aligned to its own
@@ -823,7 +823,7 @@ int v3d_depth_metrics_2d(const float* pred, int hp, int wp, const int32_t* row_s
  *   that prediction row r / column c is scored against (the index tables of the nearest resize H -> h, W -> w that the reference
  *   applies to the ground truth; entries are clamped to the ground truth); both NULL = identity, then H == h and W == w.
  * Per pixel (i, r, c): gf = gt[i, row_src[r], col_src[c]], g = double(gf), pf = pred[i, r, c], p = double(pf).
- *   Metrics: the per-pixel rule of v3d_depth_metrics_2d above with valid_mode 0, the same code (csrc/depth_pixel.h): n_pv, n_m,
+ *   Metrics: the per-pixel rule of v3d_depth_metrics_2d above with valid_mode 0, the same code (csrc/depth2d.h): n_pv, n_m,
  *   S_rel, S_diff, S_inv, S_sqrel, S_sq, c1, c2, c3 with m = g >= 0.5 and g < 65.0, and its deviation (a pixel outside m
  *   contributes nothing).
  *   Loss: where gf != 0.0f (an fp32 comparison; a NaN ground truth is in this mask, as in the reference): n_l += 1 and

@@ -84,6 +84,25 @@ def test_unaligned_bases(cuda):
     assert same_bits(got, run(cuda, g['pred'][1:], g['gt'][1:], g['interval']))
 
 
+@pytest.mark.parametrize('H,W,unaligned', [(97, 131, False), (7, 5, False), (97, 131, True)],
+                         ids=['97x131', '7x5', '97x131-unaligned'])
+def test_metrics_columns_equal_the_2d_metrics_bit_for_bit(cuda, H, W, unaligned):
+    """Equal sizes, fp32 ground truth, no validity: v3d_depth_metrics_2d walks the ground truth and v3d_depth_supervision_f32 the
+    prediction, pixel for pixel the same lanes in the same order with the same rule (csrc/depth2d.h), so columns 0-8 and counts
+    0-4 are the same bits.  3 images of 97 x 131 = 12 707 pixels: two slices, a partial last group, rows ending inside groups;
+    7 x 5: W < 8; [1:] of a 4-image allocation: neither base is 16-byte aligned (12 707 floats in)."""
+    loss, m2d = v3d('loss'), v3d('metrics2d')
+    pred, gt = (torch.from_numpy(a).to(cuda) for a in oracle.scene(3, H, W, H, W, seed=H))
+    if unaligned:
+        pred, gt = (torch.cat((t[:1], t))[1:] for t in (pred, gt))
+        assert pred.is_contiguous() and gt.is_contiguous() and pred.data_ptr() % 16 != 0 and gt.data_ptr() % 16 != 0
+    sup, met = record(loss.supervise(pred, gt, 0.05)), record(m2d.depth_metrics(pred, gt))
+    assert met['counts'].shape == (3, 5) and met['per_image'].shape == (3, 9) and sup['counts'][0, 1] > 0
+    assert np.array_equal(sup['counts'][:, :5], met['counts'])
+    assert np.array_equal(sup['per_image'][:, :9].view(np.uint64), met['per_image'].view(np.uint64))
+    assert np.array_equal(sup['mean'][:9].view(np.uint64), met['mean'].view(np.uint64))
+
+
 def test_resize_equals_the_reduced_ground_truth_through_the_identity_path(cuda):
     for name in ('S_sup_a', 'S_sup_c'):
         g = load(name)

@@ -659,7 +659,7 @@ CASES.append(Case(
     bound='metrics2d_oracle.check through test_metrics2d_gpu.assert_record: counts and fp32 columns exact, float64 columns 1e-10',
     sections=lambda lib, i: {'depth_metrics': lib.v3d_depth_metrics_workspace_bytes(i['n'], i['H'], i['W'])},
     groups=lambda i: _slices(i, i['H'] * i['W']), rule_on='big',
-    constants=(('kSlice = 8192', 'depthmetrics.hip:36'), ('kGroup = 8', 'depthmetrics.hip:37'))))
+    constants=(('kSlice = 8192', 'depth2d.h:38'), ('kGroup = 8', 'depth2d.h:39'))))
 
 
 def _sup_make(size):
@@ -692,7 +692,7 @@ CASES.append(Case(
     bound='supervision_oracle.check through test_supervision_gpu.assert_record: counts and fp32 columns exact, float64 columns 1e-10',
     sections=lambda lib, i: {'supervision': lib.v3d_depth_supervision_workspace_bytes(i['n'], i['H'], i['W'])},
     groups=lambda i: _slices(i, i['H'] * i['W']), rule_on='big',
-    constants=(('kSlice = 8192', 'supervision.hip:32'), ('kGroup = 8', 'supervision.hip:33'))))
+    constants=(('kSlice = 8192', 'depth2d.h:38'), ('kGroup = 8', 'depth2d.h:39'))))
 
 
 # ---- order statistics -------------------------------------------------------------------------------------------------------------------

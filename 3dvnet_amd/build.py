@@ -94,7 +94,7 @@ def build(force=False, verbose=False, strict=False):
             isa_check.check_no_scratch(os.path.join(objdir, 'backproject_backward.o'), 'backproject_[a-z]*_backward_kernel',
                                        strict=strict)
             # the sparse interpolation's backward: the 8 slots, weights and gradient rows of a lane in flight stay in registers
-            isa_check.check_no_scratch(os.path.join(objdir, 'sparse.o'), 'interp_backward_[a-z]*_kernel', strict=strict)
+            isa_check.check_no_scratch(os.path.join(objdir, 'sparse_interp.o'), 'interp_backward_[a-z]*_kernel', strict=strict)
             # the sparse convolution's weight gradient: up to 4 x 4 accumulator blocks (64 registers) and the 8 staged rows of a lane
             isa_check.check_no_scratch(os.path.join(objdir, 'gemm_wgrad.o'), 'sparse_conv_wgrad_[a-z_]*kernel', strict=strict)
             # confidence: the running maximum, the denominator and the two plane indices of a pixel stay in registers

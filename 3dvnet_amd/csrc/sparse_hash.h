@@ -1,5 +1,5 @@
 // Open-addressing hash table over packed (batch, x, y, z) sparse-tensor coordinates: device-side lookup shared by
-// sparse.hip (table build, neighbour tables, interpolation) and decoder.hip (fused hypothesis decoder).
+// sparse.hip (table build, neighbour tables) and, through sparse_interp.h, sparse_interp.hip (interpolation, the fused decoder's corners).
 #pragma once
 #include "v3d_common.h"
 

@@ -2,7 +2,7 @@
 and ``SparseUNet`` with the reference's constructor arguments, ``forward`` signatures, return
 structures and ``state_dict`` keys (MinkowskiEngine parameter naming: ``.kernel``, ``.gn.weight``).
 MinkowskiEngine is replaced by hash-indexed neighbour tables + the matrix-core gather-GEMM of
-``lib3dvnet_hip.so`` (csrc/sparse.hip, csrc/gemm_*.hip; fp32 storage and accumulation, MFMA operands per
+``lib3dvnet_hip.so`` (csrc/sparse.hip, csrc/sparse_interp.hip, csrc/gemm_*.hip; fp32 storage and accumulation, MFMA operands per
 the module's ``precision``: 'split_bf16' = three bf16 products per fp32 product (default), 'fp32' = exact-fp32
 MFMA); torch_scatter's max is a per-voxel segment reduction (csrc/segment.hip; the GEMM epilogue's fused
 scatter-max remains available through ``PackedGemm(pool=...)``).  No CPU fallback.

@@ -22,7 +22,7 @@ the image features and the stage-1 depth.  Its node saves the features, the dept
 
 The consumer of those hypotheses is the hypothesis decoder (``mv3d/subnetworks/refinement.py:28-44``, ``lightningmodel.py:
 237-241``).  One piece of it has no usable stock route: the sparse trilinear interpolation, whose stock formulation materialises
-nq * 8 * C floats per level.  Its backward is ``v3d_sparse_interp_backward_f32`` (``csrc/sparse.hip``): a per-row sum through an
+nq * 8 * C floats per level.  Its backward is ``v3d_sparse_interp_backward_f32`` (``csrc/sparse_interp.hip``): a per-row sum through an
 inverted index of the forward's corner table, without atomics, bitwise reproducible:
 
   * ``SparseInterpolate`` / ``sparse_interpolate``       one level at the hypothesis points -> level features;

@@ -31,7 +31,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-CHUNK = 512                   # kInterpBwdChunk of csrc/sparse.hip
+CHUNK = 512                   # kInterpBwdChunk of csrc/sparse_interp.hip
 
 
 def timed(fn, warmup, repeats):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Developer: hash-probe statistics of decoder_corner_kernel on the cfg3 scene (library built with -DV3D_CORNER_STATS:
-python scripts/build_variant.py decoder.hip cstats -DV3D_CORNER_STATS; V3D_LIB_OVERRIDE=3dvnet_amd/build/ablate/lib_cstats.so)."""
+python scripts/build_variant.py sparse_interp.hip cstats -DV3D_CORNER_STATS; V3D_LIB_OVERRIDE=3dvnet_amd/build/ablate/lib_cstats.so)."""
 import ctypes, importlib, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 syn = importlib.import_module('3dvnet_amd.synthetic'); lm = importlib.import_module('3dvnet_amd.lightningmodel'); libm = importlib.import_module('3dvnet_amd._lib')

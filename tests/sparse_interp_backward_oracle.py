@@ -1,4 +1,4 @@
-"""Plain checker of the backward of the sparse trilinear interpolation (csrc/sparse.hip, v3d_sparse_interp_backward_f32) -- a
+"""Plain checker of the backward of the sparse trilinear interpolation (csrc/sparse_interp.hip, v3d_sparse_interp_backward_f32) -- a
 checker, not a product path.  NumPy only, built on tests/sparse_oracle.py, whose ``corner_table`` restates the forward's corner
 rows and fp32 weights bit for bit.  The operation is the adjoint of the interpolation with respect to the level features:
 
@@ -32,7 +32,7 @@ import numpy as np
 import sparse_oracle as so
 
 U = 2.0 ** -24
-CHUNK = 512                          # kInterpBwdChunk of csrc/sparse.hip (test_sparse_interp_backward_oracle.py compares them)
+CHUNK = 512                          # kInterpBwdChunk of csrc/sparse_interp.hip (test_sparse_interp_backward_oracle.py compares them)
 RES = 0.0625
 MIN_PTS = np.array([[-1.25, 0.5, 3.0], [2.0, -0.75, 0.0625]], dtype=np.float32)
 SIDE = 5

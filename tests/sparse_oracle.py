@@ -1,5 +1,5 @@
 """Plain checker of the sparse-structure layer (csrc/sparse_hash.h, csrc/sparse.hip, the key helpers of csrc/voxelize.hip and the
-corner table of csrc/decoder.hip) -- a checker, not a product path.  NumPy and Python only; it does not import the package.
+interpolation and the decoder's corner table of csrc/sparse_interp.hip) -- a checker, not a product path.  NumPy and Python only; it does not import the package.
 
   * ``lookup``          a Python dict over (b, x, y, z) tuples: row of each query coordinate, or -1.  No hashing of ours, no
                         packed keys: whatever the device table aliases, drops or fails to find shows as a difference.

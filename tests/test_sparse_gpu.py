@@ -5,10 +5,11 @@ restated in NumPy; tests/test_sparse_oracle.py pins it on the CPU):
     batch ids 0 / 1 / 65535, coordinates -8 and 65519 on every axis, a full 12^3 block, and probe chains that wrap past the last slot;
   * the key helpers of csrc/voxelize.hip (sort/unique, lower bound, strided keys, unpack): exact equality, unsigned order of keys with
     bit 63 set, true floor below zero;
-  * v3d_sparse_interp_f32 itself: bit equality where the arithmetic is exact, |out - ref64| <= 9 u S everywhere else (u = 2^-24,
-    S = sum_k |w_k f_k|; derivation in sparse_oracle.py), exact zeros where no corner is present, every channel count and the
-    wide-row layout of the decoder;
-  * the corner table of the fused decoder (csrc/decoder.hip) against the unfused chain at the same edges.
+  * v3d_sparse_interp_f32 itself (csrc/sparse_interp.hip): bit equality where the arithmetic is exact, |out - ref64| <= 9 u S
+    everywhere else (u = 2^-24, S = sum_k |w_k f_k|; derivation in sparse_oracle.py), exact zeros where no corner is present, every
+    channel count and the wide-row layout of the decoder;
+  * the corner table of the fused decoder (decoder_corner_kernel, csrc/sparse_interp.hip) against the unfused chain at the same edges,
+    and against the table of v3d_sparse_interp_f32 (interp_corners_kernel) entry by entry, rows and weight bits.
 
 No number here comes from the kernels under test.  Every case that its inputs could make vacuous asserts that they do not.
 
@@ -680,3 +681,144 @@ def test_fused_decoder_and_unfused_chain_at_the_edges(n_hyp, scene, cuda):
         assert float(p_u.max()) > 0.5
     np.testing.assert_allclose(p_f, p_u, rtol=0, atol=1e-4)
     np.testing.assert_allclose(e_f, e_u, rtol=0, atol=2e-5)
+
+
+# ---- the decoder's corner table and the interpolation's corner table are the same table ---------------------------------------------
+
+TWIN_RES = 0.0625                                                               # 2^-4; the level minima are multiples of it
+TWIN_MIN = np.array([[-1.0, 0.5, 2.0], [3.0, -2.0, 0.25]], dtype=np.float32)
+TWIN_FAR = 60000                                                               # a multiple of every stride used: the last corner looked up
+
+
+def _twin_levels(strides):
+    """Three hashed levels of a few hundred voxels, finest first, widths 64 / 128 / 128 (the problem of workspace_cases._dec_make):
+    a half-filled 7^3 block in two batch elements, coarsened by floor division, plus rows at the ends of the range the corner rule
+    looks up (-8, or the stride's multiple above it; 60 000).  Row 0 is the row one stride beyond 60 000: in the table, never a
+    corner -- so a decoder entry (0, 0) can only be an absent corner."""
+    rng = np.random.default_rng(330 + sum(strides))
+    fine = _block(7, 0, batches=[0, 1])
+    fine = fine[rng.random(fine.shape[0]) < 0.5]
+    levels = []
+    for ts, C in zip(strides, (64, 128, 128)):
+        low = -(so.GUARD // ts) * ts
+        ends = [(0, low, low, low), (1, 0, low, 0), (0, TWIN_FAR, 0, 0), (1, 0, 0, TWIN_FAR)]
+        rows = {(int(r[0]),) + tuple(int(v) // ts * ts for v in r[1:]) for r in fine} | set(ends)
+        rows = np.array(sorted(rows), dtype=np.int64)
+        coords = np.concatenate((np.array([(0, TWIN_FAR + ts, 0, 0)], dtype=np.int64), rows[rng.permutation(rows.shape[0])]))
+        levels.append(dict(coords=coords, ts=ts, res=TWIN_RES * ts, low=low, feats=rng.standard_normal((coords.shape[0], C)).astype(np.float32)))
+    return levels
+
+
+def _twin_queries(n_hyp, seed):
+    """The edge set of test_interp_away_from_the_occupied_voxels in base voxels, exact in fp32: inside the block on a quarter-voxel
+    grid, on lattice points, 1 / 8 / 9 / 100 voxels below the minimum, either side of 60 000, far outside, in both batch elements;
+    hypothesis h of a point is h quarter-voxel steps away from it."""
+    rng = np.random.default_rng(seed)
+    L = float(TWIN_FAR)
+    groups = [(0, [(0, 0, 0), (6, 6, 6), (4, 4, 4), (0, 6, 4), (6, 0, 2), (3, 3, 3), (12, 6, 0)]),
+              (0, [(-1, .25, .5), (-1, 0, 0), (-8, -8, -8), (-7.75, -7.5, -8), (-8, 0, 0), (-8.5, 0, 0), (-8, .5, .5), (-8.25, 1, 1),
+                   (-6, -6, -6), (-5.5, -6, -5.75), (-6.5, 0, 0), (-9, .5, .5), (-9, 0, 0), (-9.5, -9.5, -9.5), (-12, 0, 0),
+                   (-100, 1, 1), (1, -100, 1), (1, 1, -100)]),
+              (0, [(L - .5, 0, 0), (L, 0, 0), (L + .5, 0, 0), (L + 1, 0, 0), (L + 10, 5, 5), (L - 1, .5, .5), (L - 6, 0, 0), (65519, 0, 0),
+                   (70000, 1, 1), (1.6e7, 0, 0), (0, 1.6e7, 0), (1.6e7, 1.6e7, 1.6e7)]),
+              (1, [(0, 0, L), (0, 0, L + .5), (.5, .5, L - .5), (0, -8, 0), (.5, -8.25, 0), (0, -6, 0), (0, 0, L + 1), (2, 4, 6)])]
+    g = np.concatenate([np.array(q, dtype=np.float64) for _, q in groups] + [rng.integers(0, 7, (30, 3)).astype(np.float64),
+                                                                            np.round(rng.uniform(-1, 7, (114, 3)) * 4) / 4])
+    pts_batch = np.concatenate([np.full(len(q), b) for b, q in groups] + [rng.integers(0, 2, 144)]).astype(np.int64)
+    step = np.round(rng.standard_normal((g.shape[0], 1, 3)) * 2) / 4
+    g = g[:, None, :] + step * np.arange(n_hyp)[None, :, None]
+    p64 = TWIN_MIN[pts_batch].astype(np.float64)[:, None, :] + g * TWIN_RES
+    pts = p64.astype(np.float32)
+    near = np.abs(g).max(axis=2) < 1e6
+    assert np.array_equal(pts[near].astype(np.float64), p64[near])               # the queries ARE the intended positions
+    return pts, pts_batch
+
+
+def _twin_case(strides, n_hyp):
+    """Levels, queries and the checker's corner tables, with everything that makes the comparison worth running asserted on the
+    checker alone (no device call)."""
+    levels = _twin_levels(strides)
+    pts, pts_batch = _twin_queries(n_hyp, seed=340 + n_hyp)
+    n_pts = pts.shape[0]
+    assert n_pts % 32 != 0 and set(pts_batch.tolist()) == {0, 1}                 # a ragged last tile of the fused kernel
+    assert 300 < levels[0]['coords'].shape[0] < 400
+    for lv in levels:
+        ts, coords = lv['ts'], lv['coords']
+        assert coords.shape[0] >= 16 and (coords[:, 1:] % ts == 0).all() and np.unique(coords, axis=0).shape[0] == coords.shape[0]
+        rows, w, qc = so.corner_table(coords, ts, pts, pts_batch, n_hyp, TWIN_MIN, lv['res'])
+        present = rows >= 0
+        assert present.sum() >= 50 and (~present).sum() >= 50
+        assert (present & (w == 0)).any() and (present & (w == 1)).any()        # on a lattice plane / on a lattice point
+        assert not (rows == 0).any()                                             # row 0 lies past the upper guard
+        table = {tuple(r): i for i, r in enumerate(coords.tolist())}
+        found = set(rows[present].tolist())
+        low = lv['low']
+        assert {table[(0, low, low, low)], table[(1, 0, low, 0)], table[(0, TWIN_FAR, 0, 0)], table[(1, 0, 0, TWIN_FAR)]} <= found
+        lo = np.floor(qc / np.float32(ts)) * np.float32(ts)                      # lower corner per axis
+        hyp0 = np.arange(n_pts) * n_hyp
+        below = (lo[hyp0] < -so.GUARD).any(axis=1) & (lo[hyp0] > -20).all(axis=1)
+        beyond = (lo[hyp0, 0] + ts > so.INTERP_MAX) & (lo[hyp0, 0] <= so.INTERP_MAX)
+        assert below.sum() >= 3 and beyond.sum() >= 1                            # just past either guard: corners that are not looked up
+        assert (lo[hyp0] == low).any() and (lo[hyp0] == TWIN_FAR).any()          # ... and on the last coordinate that is
+        lv['rows'] = rows
+    return levels, pts, pts_batch
+
+
+@pytest.mark.parametrize('n_hyp', [3, 8])
+@pytest.mark.parametrize('strides', [(1, 2, 4), (1, 3, 6)], ids=['pow2', 'div'])
+def test_decoder_and_interp_corner_tables_are_the_same_table(strides, n_hyp, cuda):
+    """v3d_decoder_fused_f32 (inference) and v3d_sparse_interp_f32 (training, forward and backward) each leave their corner table in
+    their workspace.  Entry by entry -- every query, level and corner -- the decoder's (row, weight bits) is (0, 0) exactly where
+    the interpolation's row is -1, and holds the same row and the same weight bits everywhere else; the rows of both are the
+    checker's.  Strides (1, 2, 4) run the kernels' reciprocal path, (1, 3, 6) the division path."""
+    import workspace_cases as wc
+    levels, pts, pts_batch = _twin_case(strides, n_hyp)
+    libm, lib = _libs()
+    s = libm.stream_ptr(cuda)
+    n_pts, n_q = pts.shape[0], pts.shape[0] * n_hyp
+    p, pb, mn = _to(pts, cuda, torch.float32), _to(pts_batch, cuda, torch.int64), _to(TWIN_MIN, cuda, torch.float32)
+    tabs, feats = [], []
+    for lv in levels:
+        _, table = _build(lv['coords'], cuda)
+        assert _status(table, lv['coords'].shape[0], cuda) == OK
+        tabs.append(table)
+        feats.append(_to(lv['feats'], cuda, torch.float32))
+    # the decoder's table: [n_q][3 levels][8 corners] (row, weight bits) at the head of its workspace
+    handles, w_last, b_last = wc._decoder(cuda).packed_handles(cuda)
+    vp = ctypes.c_void_p
+    arr = lambda ctype, vals: (ctype * 3)(*vals)
+    nb = lib.v3d_decoder_fused_workspace_bytes(n_pts, n_hyp)
+    ws = torch.full((nb,), 0xA5, dtype=torch.uint8, device=cuda)
+    vals = torch.linspace(-0.1, 0.1, n_hyp).to(cuda)
+    preds, expect = torch.empty((n_pts, n_hyp), device=cuda), torch.empty(n_pts, device=cuda)
+    rc = lib.v3d_decoder_fused_f32(arr(vp, handles), w_last.data_ptr(), b_last.data_ptr(), arr(vp, [t.data_ptr() for t in tabs]),
+                                   arr(ctypes.c_int, [lv['coords'].shape[0] for lv in levels]), arr(vp, [f.data_ptr() for f in feats]),
+                                   arr(ctypes.c_int, [lv['feats'].shape[1] for lv in levels]), arr(ctypes.c_int, [lv['ts'] for lv in levels]),
+                                   arr(vp, [mn.data_ptr()] * 3), arr(ctypes.c_float, [lv['res'] for lv in levels]), p.data_ptr(),
+                                   pb.data_ptr(), None, 0, n_pts, n_hyp, vals.data_ptr(), preds.data_ptr(), expect.data_ptr(), None,
+                                   ws.data_ptr(), nb, s)
+    assert rc == OK, lib.v3d_last_error()
+    torch.cuda.synchronize()
+    assert torch.isfinite(preds).all()
+    dec = ws.cpu().numpy()[:n_q * 24 * 8].view(np.uint32).reshape(n_q, 3, 8, 2)
+    # the interpolation's table, level by level: [crow n_q * 8 int32][cw n_q * 8 float32], 256-byte aligned sections
+    nbi = lib.v3d_sparse_interp_workspace_bytes(n_pts, n_hyp)
+    assert nbi == 2 * ((n_q * 32 + 255) // 256 * 256)
+    for l, lv in enumerate(levels):
+        C = lv['feats'].shape[1]
+        wsi = torch.full((nbi,), 0xA5, dtype=torch.uint8, device=cuda)
+        out = torch.empty((n_q, C), device=cuda)
+        assert lib.v3d_sparse_interp_f32(tabs[l].data_ptr(), lv['coords'].shape[0], feats[l].data_ptr(), C, lv['ts'], p.data_ptr(),
+                                         pb.data_ptr(), n_pts, n_hyp, mn.data_ptr(), float(lv['res']), out.data_ptr(), C, 0,
+                                         wsi.data_ptr(), nbi, s) == OK
+        raw = wsi.cpu().numpy()
+        crow = raw[:n_q * 32].view(np.int32).reshape(n_q, 8)
+        cw = raw[nbi // 2:nbi // 2 + n_q * 32].view(np.uint32).reshape(n_q, 8)
+        d_row, d_w = dec[:, l, :, 0], dec[:, l, :, 1]
+        assert np.array_equal(crow, lv['rows'])                                  # the checker's rows, -1 included
+        absent = crow == -1
+        assert np.array_equal(absent, (d_row == 0) & (d_w == 0))
+        assert np.array_equal(d_row[~absent], crow[~absent].astype(np.uint32))
+        assert np.array_equal(d_w[~absent], cw[~absent])
+        print('stride %d, n_hyp=%d: %d present and %d absent corners, %d present with weight 0: rows and weight bits equal'
+              % (lv['ts'], n_hyp, (~absent).sum(), absent.sum(), (~absent & (cw == 0)).sum()))

@@ -1,4 +1,4 @@
-"""GPU: v3d_sparse_interp_backward_f32 (csrc/sparse.hip) through the C ABI and through training.SparseInterpolate, per element
+"""GPU: v3d_sparse_interp_backward_f32 (csrc/sparse_interp.hip) through the C ABI and through training.SparseInterpolate, per element
 against tests/sparse_interp_backward_oracle.py (float64 sums over the corner table of tests/sparse_oracle.py; pinned on the CPU by
 tests/test_sparse_interp_backward_oracle.py):
 

@@ -23,7 +23,7 @@ def case_orc(request):
 
 
 def test_chunk_constant_is_the_kernels():
-    src = open(os.path.join(ROOT, '3dvnet_amd', 'csrc', 'sparse.hip')).read()
+    src = open(os.path.join(ROOT, '3dvnet_amd', 'csrc', 'sparse_interp.hip')).read()
     assert int(re.search(r'constexpr int kInterpBwdChunk = (\d+);', src).group(1)) == sbo.CHUNK
     assert sbo.N_HOT > 3 * sbo.CHUNK and sbo.N_HOT % sbo.CHUNK != 0
 

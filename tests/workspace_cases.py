@@ -440,8 +440,8 @@ CASES.append(Case(
     bound='sparse_oracle.neighbours exact, sparse_oracle.interp within 9 u S (tests/test_sparse_gpu.py::test_interp_generic_queries_within_nine_u_s)',
     sections=lambda lib, i: {'table': lib.v3d_hash_bytes(i['n']), 'interp': lib.v3d_sparse_interp_workspace_bytes(i['n_pts'], i['n_hyp'])},
     groups=lambda i: [('hash_insert / neighbors', i['n'], 256), ('interp_corners_kernel', i['n_pts'] * i['n_hyp'] * 8, 256)],
-    constants=(('hash_insert_kernel<<<(n + 255) / 256, 256', 'sparse.hip:133'),
-               ('interp_corners_kernel<<<(unsigned)((nq * 8 + 255) / 256), 256', 'sparse.hip:178')), rejected='rejected',
+    constants=(('hash_insert_kernel<<<(n + 255) / 256, 256', 'sparse.hip:74'),
+               ('interp_corners_kernel<true><<<(unsigned)((nq * 8 + 255) / 256), 256', 'sparse_interp.hip:271')), rejected='rejected',
     paired=True))
 
 
@@ -1250,7 +1250,7 @@ def _decoder_sd():
 
 def _dec_make(size):
     import sparse_oracle as so
-    n_pts, side, n_hyp = {'small': (150, 7, 3), 'big': (330, 9, 3)}[size]        # 32 points per tile (decoder.hip:102)
+    n_pts, side, n_hyp = {'small': (150, 7, 3), 'big': (330, 9, 3)}[size]        # 32 points per tile (decoder.hip:101)
     rng = np.random.default_rng(120 + n_pts)
     g = np.stack(np.meshgrid(np.arange(2), np.arange(side), np.arange(side), np.arange(side), indexing='ij'), -1).reshape(-1, 4)
     fine = g[rng.random(g.shape[0]) < 0.5].astype(np.int64)
@@ -1323,8 +1323,8 @@ CASES.append(Case(
     sections=lambda lib, i: {'fused': lib.v3d_decoder_fused_workspace_bytes(i['n_pts'], i['n_hyp'])},
     groups=lambda i: [('index kernel: 8 corners x 3 levels per hypothesis point', i['n_pts'] * i['n_hyp'], 256),
                       ('decoder_fused_kernel: tiles of kDPtsTile = 32 points', i['n_pts'], 32)],
-    constants=(('kDPtsWave = 4, kDPtsTile = kDPtsWave * kDWaves', 'decoder.hip:102'), ('kDWaves = 8', 'decoder.hip:101'),
-               ('decoder_corner_kernel<true><<<(unsigned)((n_thr + 255) / 256), 256', 'decoder.hip:839')),
+    constants=(('kDPtsWave = 4, kDPtsTile = kDPtsWave * kDWaves', 'decoder.hip:101'), ('kDWaves = 8', 'decoder.hip:100'),
+               ('decoder_corner_kernel<true><<<(unsigned)((n_thr + 255) / 256), 256', 'sparse_interp.hip:286')),
     inout=('table0', 'table1', 'table2')))
 
 
@@ -1441,11 +1441,11 @@ CASES.append(Case(
     sections=lambda lib, i: {'table': lib.v3d_hash_bytes(i['n']),
                              'interp_backward': lib.v3d_sparse_interp_backward_workspace_bytes(i['n'], INTERP_BWD_C, i['n_pts'], i['n_hyp'])},
     groups=_ibwd_groups,
-    constants=(('kInterpBwdChunk = 512', 'sparse.hip:200'),
-               ('interp_backward_segment_kernel<<<(unsigned)((nq * 8 + 255) / 256), 256', 'sparse.hip:368'),
-               ('interp_backward_count_kernel<<<(unsigned)(((long long)n_in + 256) / 256), 256', 'sparse.hip:374'),
-               ('interp_backward_chunk_kernel<true><<<blocks, 256', 'sparse.hip:381'),
-               ('interp_backward_combine_kernel<<<(unsigned)(((long long)n_in * tpc + 255) / 256), 256', 'sparse.hip:386')),
+    constants=(('kInterpBwdChunk = 512', 'sparse_interp.hip:124'),
+               ('interp_backward_segment_kernel<<<(unsigned)((nq * 8 + 255) / 256), 256', 'sparse_interp.hip:347'),
+               ('interp_backward_count_kernel<<<(unsigned)(((long long)n_in + 256) / 256), 256', 'sparse_interp.hip:358'),
+               ('interp_backward_chunk_kernel<true><<<blocks, 256', 'sparse_interp.hip:365'),
+               ('interp_backward_combine_kernel<<<(unsigned)(((long long)n_in * tpc + 255) / 256), 256', 'sparse_interp.hip:370')),
     paired=True))
 
 

@@ -186,6 +186,11 @@ SIGNATURES = {
     'v3d_sparse_conv_weight_grad_workspace_bytes': (c_size_t, [c_int] * 4),
     'v3d_sparse_conv_weight_grad_f32': (c_int, [c_void_p, c_int, c_void_p, ctypes.c_longlong, c_int, c_void_p, c_int, c_int, c_int,
                                                 c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'v3d_segment_max_arg_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                                        c_void_p]),
+    'v3d_segment_sum_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    'v3d_pointnet_pool_backward_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
+                                               c_int, c_void_p, c_int, c_void_p]),
 }
 
 

@@ -1,6 +1,6 @@
-"""Training of the cost-volume stage (stage 1), of the entry of stage 2, of the hypothesis decoder and of the sparse U-Net: the pieces
-of ``mv3d/subnetworks/mvsnet.py:186-227``, of the initial depth supervision (``mv3d/lightningmodel.py:57-63``), of the
-back-projected variance, of ``run_pointflow`` and of ``SparseUNet.forward`` with a backward pass.
+"""Training of the cost-volume stage (stage 1) and of stage 2 -- its entry, PointNet and the voxel pooling, the sparse U-Net and the
+hypothesis decoder: the pieces of ``mv3d/subnetworks/mvsnet.py:186-227``, of the initial depth supervision
+(``mv3d/lightningmodel.py:57-63``), of the back-projected variance, of ``model_scene`` and of ``run_pointflow`` with a backward pass.
 
 Only one operation of stage 1 has no stock-torch route that is usable on the device: the fused warp + variance (rows
 A1-A4).  Its backward is ``csrc/psv_backward.hip`` behind ``v3d_psv_variance_backward_f32`` (include/v3d.h); like the forward
@@ -41,17 +41,28 @@ GroupNorm, ReLU, the residual add and the 1x1 ``feat_adj`` are stock differentia
   * ``sparse_unet``                                      ``SparseUNet.forward`` -> the level features, differentiable in the
                                                          input F and in every U-Net parameter; plugs into ``pointflow_offset``.
 
+The producer of F is PointNet (``mv3d/subnetworks/scenemodeling.py:116-144``).  Its stock graph keeps ``cat(x, pool[idx])``
+[Np, 2H] three times, sums the pooled gradients with ``index_add`` atomics and, with torch's ``scatter_reduce('amax')``, splits a
+gradient among equal values where ``torch_scatter`` hands it to one row.  Here it is one node over three streaming kernels
+(``csrc/segment_backward.hip``: ``v3d_segment_max_arg_f32``, ``v3d_segment_sum_f32``, ``v3d_pointnet_pool_backward_f32``; no atomics,
+bitwise reproducible) and ``torch.mm``:
+
+  * ``PointNetFunction`` / ``pointnet``                  ``PointNet.forward`` (the same bits) -> x and the twelve parameters;
+  * ``scene_features``                                   the differentiable twin of ``model_scene``: point cloud -> voxels (data)
+                                                         -> PointNet -> ``sparse_unet``; with ``pointflow_offset`` and ``masked_mae``
+                                                         a loss on a refined depth reaches ``depth_pred``, ``img_feats`` and every
+                                                         parameter of stage 2.
+
 Cameras, plane depths, offsets and edges are data (no gradient), as in the reference, which also builds every sampling grid under
 ``no_grad``.  The image-feature gradients are summed with fp32 atomic adds: their last bits can differ from call to call (DESIGN.md
-4.1b, 4.1c).  Out of scope: the rest of stage 2 (PointNet and the voxel pooling: they connect to the gradient of F produced
-here), stage 3, the native backbone, the split / channel-last variance formats, ``PL3DVNet.forward`` in training mode,
-an optimiser loop.  No CPU fallback.
+4.1b, 4.1c).  Out of scope: stage 3, the native backbone, the split / channel-last variance formats, ``PL3DVNet.forward`` in
+training mode, an optimiser loop.  No CPU fallback.
 """
 import torch
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from . import _lib, lightningmodel, mvsnet
+from . import _lib, lightningmodel, mvsnet, utils
 
 
 def _feature_gradient(features, grad_var, shape, call):
@@ -490,6 +501,169 @@ def sparse_unet(unet, feats, xs):
             x = residual(blk, x, i - 1)
         out.append(x)
     return out
+
+
+_POINTNET_LAYERS = ('fc_pos', 'fc1', 'fc2', 'fc3', 'fc4', 'fc_out')
+
+
+class PointNetFunction(torch.autograd.Function):
+    """``PointNet.forward`` (scenemodeling.py:127-144) as ONE node with the gradients to ``x`` and to the twelve parameters
+    (DESIGN.md 4.1f).  The forward is the inference forward call for call in ``pn.precision`` (the same bits), with
+    ``v3d_segment_max_arg_f32`` in place of ``v3d_segment_max_f32``: it names the row that won each pooled value.  The node saves
+    ``x``, ``h0 = fc_pos(x)``, the four layer outputs ``x1..x4`` [Np, H], the four pools and winner tables [Nv, H] and the segment
+    list: nothing of width 2H (``cat(x, pool[idx])`` is never built, in neither direction).
+
+    The backward runs in fp32 for both precisions.  Dense products are ``torch.mm``; what autograd would do with ``index_add``
+    (atomics) and ``cat`` is three kernels: the sum of a voxel's gradient rows S = ``v3d_segment_sum_f32`` (the gradient of the
+    pooled half of ``fc_k`` is a function of the voxel alone, so its products run over Nv rows), and
+    ``v3d_pointnet_pool_backward_f32``, which masks the direct path by the ReLU and hands the pooled gradient to the ONE row that
+    won (torch_scatter's rule; torch's own ``scatter_reduce('amax')`` splits it among ties)."""
+
+    @staticmethod
+    def forward(ctx, pn, trace, idx32, n_idx, x, *params):
+        lib = _lib.load()
+        dev = x.device
+        pn._dev = dev
+        g = pn._cache.get(pn._build, dev)
+        pr = pn.precision
+        xc = x.detach().contiguous().float()
+        Np, H = xc.shape[0], pn.hidden_dim
+        with torch.cuda.device(dev):
+            stream = _lib.stream_ptr(dev)
+            perm = torch.empty(Np, dtype=torch.int32, device=dev)
+            offs = torch.empty(n_idx + 1, dtype=torch.int32, device=dev)
+            ws = pn._ws.get('segcsr', lib.v3d_segment_csr_workspace_bytes(Np), dev)
+            _lib.check(lib.v3d_segment_csr(idx32.data_ptr(), Np, n_idx, perm.data_ptr(), offs.data_ptr(), ws.data_ptr(), ws.numel(),
+                                           stream), 'v3d_segment_csr')
+
+            def pooled(t):
+                pool = torch.empty((n_idx, H), dtype=torch.float32, device=dev)
+                arg = torch.empty((n_idx, H), dtype=torch.int32, device=dev)
+                _lib.check(lib.v3d_segment_max_arg_f32(t.data_ptr(), t.stride(0), perm.data_ptr(), offs.data_ptr(), n_idx, H,
+                                                       pool.data_ptr(), H, arg.data_ptr(), H, stream), 'v3d_segment_max_arg_f32')
+                return pool, arg
+
+            h0 = g['fc_pos'](Np, [xc], precision=pr)
+            xs = [g['fc1'](Np, [h0], relu_in=True, precision=pr)]
+            pools, args = [], []
+            for name in ('fc2', 'fc3', 'fc4', None):
+                pool, arg = pooled(xs[-1])
+                pools.append(pool)
+                args.append(arg)
+                if name is not None:
+                    xs.append(g[name](Np, [xs[-1], pool], idxs=[None, idx32], relu_in=True, precision=pr))
+            out = g['fc_out'](n_idx, [pools[-1]], relu_in=True, precision=pr)
+        if trace is not None:
+            trace.update(h0=h0, **{'x%d' % (i + 1): t for i, t in enumerate(xs)}, **{'pool%d' % (i + 1): t for i, t in enumerate(pools)},
+                         **{'arg%d' % (i + 1): t for i, t in enumerate(args)})
+        ctx.save_for_backward(x, h0, *xs, *pools, *args, idx32, perm, offs, *params)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        saved = ctx.saved_tensors
+        x, h0, xs, pools, args = saved[0], saved[1], saved[2:6], saved[6:10], saved[10:14]
+        idx32, perm, offs = saved[14:17]
+        W = saved[17::2]                                        # the six weights, in the order of _POINTNET_LAYERS
+        need_x, need = ctx.needs_input_grad[4], ctx.needs_input_grad[5:]
+        wants = [need[2 * i] or need[2 * i + 1] for i in range(6)]
+        # the chain runs down to the lowest layer anybody asks about (x lies below fc_pos)
+        lowest = -1 if need_x else min((i for i in range(6) if wants[i]), default=6)
+        grads = [None] * 12
+
+        def result(grad_x=None):
+            return (None, None, None, None, grad_x) + tuple(None if t is None else t.to(p.dtype) for t, p in zip(grads, saved[17:]))
+        if lowest == 6:
+            return result()
+        lib = _lib.load()
+        dev = x.device
+        Np, H, n_idx = h0.shape[0], h0.shape[1], pools[0].shape[0]
+        stream = _lib.stream_ptr(dev)
+
+        def segment_sum(G):
+            S = torch.empty((n_idx, H), dtype=torch.float32, device=dev)                # every element is written
+            _lib.check(lib.v3d_segment_sum_f32(G.data_ptr(), H, perm.data_ptr(), offs.data_ptr(), n_idx, H, S.data_ptr(), H, stream),
+                       'v3d_segment_sum_f32')
+            return S
+
+        def pool_backward(g_lin, x_k, g_pool, arg):
+            G = torch.empty((Np, H), dtype=torch.float32, device=dev)                   # every element is written
+            _lib.check(lib.v3d_pointnet_pool_backward_f32(_lib.ptr(g_lin), H, _lib.ptr(x_k), H, idx32.data_ptr(), g_pool.data_ptr(), H,
+                                                          arg.data_ptr(), H, Np, H, G.data_ptr(), H, stream),
+                       'v3d_pointnet_pool_backward_f32')
+            return G
+
+        def linear_grads(i, G, inputs, bias_rows):
+            # dW = [G_0^T a_0 | G_1^T a_1 ...] over (gradient rows, ReLU'd input) pairs, db = the column sums of `bias_rows`
+            if need[2 * i]:
+                parts = [Gj.t() @ a for Gj, a in inputs]
+                grads[2 * i] = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+            if need[2 * i + 1]:
+                grads[2 * i + 1] = bias_rows.sum(dim=0)
+
+        with torch.cuda.device(dev):
+            # a slice of a wider row or a stride-0 expanded tensor (a .sum() upstream) becomes one contiguous fp32 copy, [Nv, out_dim]:
+            # only torch.mm reads it
+            g = grad_out.float().contiguous()
+            linear_grads(5, g, [(g, F.relu(pools[3]))], g)
+            if lowest >= 5:
+                return result()
+            G = pool_backward(None, None, (g @ W[5]).mul_(pools[3] > 0), args[3])       # the gradient of x4
+            for k in (4, 3, 2):                                                          # fc_k reads x_{k-1} and pool_{k-1}[idx]
+                x_in, pool_in, arg_in = xs[k - 2], pools[k - 2], args[k - 2]
+                S = segment_sum(G)
+                linear_grads(k, G, [(G, F.relu(x_in)), (S, F.relu(pool_in))], S)
+                if lowest >= k:
+                    return result()
+                G = pool_backward(G @ W[k][:, :H], x_in, (S @ W[k][:, H:]).mul_(pool_in > 0), arg_in)
+            linear_grads(1, G, [(G, F.relu(h0))], G)                                     # G: the gradient of x1 = fc1(relu(h0))
+            if lowest >= 1:
+                return result()
+            G = (G @ W[1]).mul_(h0 > 0)
+            linear_grads(0, G, [(G, x.detach().float())], G)
+            return result((G @ W[0]).to(x.dtype) if need_x else None)
+
+
+def pointnet(pn, x, idx, n_idx, trace=None):
+    """``pn(x, idx, n_idx)`` of an existing ``scenemodeling.PointNet`` (the same bits, in ``pn.precision``) -> [n_idx, out_dim],
+    differentiable in ``x`` [Np, in_dim] and in the twelve parameters of ``pn`` (no second parameter set; ``state_dict`` keys
+    untouched).  ``idx`` [Np]: the voxel of each point, data.  ``trace``: a dict that receives ``h0``, ``x1..x4`` (the arguments of
+    the ReLUs), ``pool1..pool4`` and ``arg1..arg4`` (the winner rows) of the forward.  ``hidden_dim`` must be a multiple of 4 up to
+    128."""
+    mvsnet._require_cuda(x, 'training.pointnet')
+    assert x.dim() == 2 and idx.shape == (x.shape[0],)
+    params = [p for name in _POINTNET_LAYERS for p in (getattr(pn, name).weight, getattr(pn, name).bias)]
+    return PointNetFunction.apply(pn, trace, idx.to(torch.int32).contiguous(), int(n_idx), x, *params)
+
+
+def scene_features(net, depth_pred, depth_batch, img_feats, rotmats, tvecs, K, ref_src_edges, csr=None, trace=None):
+    """The differentiable twin of ``PL3DVNet.model_scene`` (lightningmodel.py:176-185) -> ``(xs, level_feats)``: ``xs`` the levels of
+    the inference U-Net (coordinate maps, tables: data), ``level_feats`` one [N_l, C_l] tensor per level with the gradient to
+    ``depth_pred`` (through the points), to ``img_feats`` (through the point features) and to every parameter of ``net.pointnet``
+    and ``net.sparse_conv``; both plug into ``pointflow_offset(net.decoder, xs, ..., level_feats=level_feats)``.
+
+    The voxel grid is data (``utils.voxelize`` on detached points) with one exception the reference has too: its anchors are
+    ``idx3d * edge + bbox_min + edge / 2`` with ``bbox_min = pts.min(dim=0)[0]`` OUTSIDE ``no_grad`` (mv3d/utils.py:39,58), so the
+    point that holds an axis' minimum receives minus the sum of that column of the PointNet input's gradient.  Taking the exact
+    zero ``bmin - bmin.detach()`` off the input's position columns keeps their bits and adds that path.  ``trace``: a dict that receives ``pts``, ``pts_feat``, ``edges``,
+    ``anchor_pts``, ``x`` (the PointNet input) and ``F`` (the U-Net input)."""
+    pts, pts_feat, pts_batch = feature_rich_pointcloud(depth_pred, depth_batch, img_feats, rotmats, tvecs, K, ref_src_edges,
+                                                       net.hparams.img_size, csr=csr)
+    with torch.no_grad():
+        anchor_pts, anchor_idx3d, anchor_batch, edges = utils.voxelize(pts, pts_batch, net.edge_len)
+    # p - (anchor + (bmin - bmin.detach())) with the exact zero taken off the difference instead: the same bits, the same
+    # gradient, and bmin's is a column sum over the points instead of an index_add (atomics) into the anchors
+    bmin = pts.min(dim=0)[0]
+    rel = pts.index_select(0, edges[1]) - anchor_pts.index_select(0, edges[0]) - (bmin - bmin.detach())
+    x = torch.cat((rel, pts_feat.index_select(0, edges[1])), dim=1)
+    feats = pointnet(net.pointnet, x, edges[0], anchor_pts.shape[0])
+    unet = net.sparse_conv
+    with torch.no_grad():
+        xs = unet(feats.detach(), anchor_pts, anchor_idx3d, anchor_batch, net.edge_len, idx_min_zero=True)
+    if trace is not None:
+        trace.update(pts=pts, pts_feat=pts_feat, edges=edges, anchor_pts=anchor_pts, x=x, F=feats)
+    return xs, sparse_unet(unet, feats, xs)
 
 
 def _conv_bn_relu(mod, x, bn_training):

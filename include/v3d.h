@@ -420,6 +420,29 @@ int v3d_segment_csr(const int32_t* seg_id, int n, int n_seg, int32_t* perm, int3
                     size_t workspace_bytes, void* stream);
 int v3d_segment_max_f32(const float* src, int ld, const int32_t* perm, const int32_t* offsets, int n_seg, int N, float* out,
                         int ld_out, void* stream);
+/* The backward of that pooling and of PointNet's cat(x, pool[idx]) (training; additive within ABI version 9).
+ * All three read whole rows 16 bytes per lane through perm / offsets of v3d_segment_csr (or seg_id itself), use no scratch
+ * buffer, no LDS and no float atomics, and return the same bits in every call.  Shapes as v3d_segment_max_f32: N a multiple of
+ * 4 up to 256, every ld a multiple of 4 and >= N; in addition every matrix must be 16-byte aligned.  Of an output's rows the
+ * first N columns are written, EVERY one of them; columns behind N and rows behind the last are never touched.
+ * Errors, before anything is enqueued: V3D_ERR_BAD_ARG for a null pointer or a misaligned matrix, V3D_ERR_BAD_SHAPE otherwise.
+ *   v3d_segment_max_arg_f32  out as v3d_segment_max_f32 (the same bits for every input without NaN) and arg [n_seg, ld_arg]
+ *     int32: the ROW of src (not the position in perm) that holds the maximum; among equal values the lowest row (rows ascend
+ *     along a segment's list: the sort is stable).  A NaN never wins; an empty segment (and one of NaN rows only) gives -inf
+ *     and -1.  This is torch_scatter's rule on the CPU (first on strict >); DESIGN.md 4.1f says what is pinned of it.
+ *   v3d_segment_sum_f32  out[s] = (the sum of the rows at the even positions offsets[s], offsets[s] + 2, ... of the list, added
+ *     in that order to +0) + (the same for the odd positions): two chains, one final addition.  An empty segment gives +0.
+ *   v3d_pointnet_pool_backward_f32  grad_x[r, c] = (x[r, c] > 0 ? grad_lin[r, c] : 0) + (arg[seg_id[r], c] == r ?
+ *     grad_pool[seg_id[r], c] : 0) for the n rows r: the ReLU mask of the direct path and the single-winner scatter of the
+ *     pooled path in one pass, every element written once.  grad_lin == NULL (x may then be NULL): the second term alone.
+ *     seg_id [n] int32 must lie in [0, rows of grad_pool and arg): the caller's contract, not checked. */
+int v3d_segment_max_arg_f32(const float* src, int ld, const int32_t* perm, const int32_t* offsets, int n_seg, int N, float* out,
+                            int ld_out, int32_t* arg, int ld_arg, void* stream);
+int v3d_segment_sum_f32(const float* src, int ld, const int32_t* perm, const int32_t* offsets, int n_seg, int N, float* out,
+                        int ld_out, void* stream);
+int v3d_pointnet_pool_backward_f32(const float* grad_lin, int ld_lin, const float* x, int ld_x, const int32_t* seg_id,
+                                   const float* grad_pool, int ld_pool, const int32_t* arg, int ld_arg, int n, int N,
+                                   float* grad_x, int ld_gx, void* stream);
 size_t v3d_sort_unique_workspace_bytes(int n);
 int v3d_sort_unique_u64(const uint64_t* keys_in, int n, uint64_t* keys_out, int* n_unique_host,
                         void* workspace, size_t workspace_bytes, void* stream);

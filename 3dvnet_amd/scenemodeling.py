@@ -131,12 +131,37 @@ class PointNet(nn.Module):
         self._cache = _PackCache(self)
         self._ws = _Workspace()
 
+    LAYERS = ('fc_pos', 'fc1', 'fc2', 'fc3', 'fc4', 'fc_out')                   # fc2..fc4 read two sources: cat(x, pool[idx])
+
     def _build(self):
         def lin(m, n_seg):
             N, Kt = m.weight.shape
             return PackedGemm(m.weight, Kt // n_seg, Kt, 1, n_seg, N, Kt // n_seg, bias=m.bias, device=self._dev)
-        return dict(fc_pos=lin(self.fc_pos, 1), fc1=lin(self.fc1, 1), fc2=lin(self.fc2, 2),
-                    fc3=lin(self.fc3, 2), fc4=lin(self.fc4, 2), fc_out=lin(self.fc_out, 1))
+        return {name: lin(getattr(self, name), 2 if name in self.LAYERS[2:5] else 1) for name in self.LAYERS}
+
+    def _segments(self, idx32, n_idx, dev):
+        """The rows grouped by voxel, once per forward (device radix sort) -> row list ``perm`` [Np] and ``offs`` [n_idx + 1]: what the
+        per-voxel reductions of csrc/segment.hip walk instead of atomics (the gather-GEMM's fused scatter-max was 80 % of a layer)."""
+        lib = _lib.load()
+        Np = idx32.shape[0]
+        perm = torch.empty(Np, dtype=torch.int32, device=dev)
+        offs = torch.empty(n_idx + 1, dtype=torch.int32, device=dev)
+        ws = self._ws.get('segcsr', lib.v3d_segment_csr_workspace_bytes(Np), dev)
+        _lib.check(lib.v3d_segment_csr(idx32.data_ptr(), Np, n_idx, perm.data_ptr(), offs.data_ptr(), ws.data_ptr(), ws.numel(),
+                                       _lib.stream_ptr(dev)), 'v3d_segment_csr')
+        return perm, offs
+
+    def _layers(self, g, x, idx32, n_idx, pooled):
+        """The layer sequence (:127-144) over the packed layers ``g`` -> (output, fc_pos(x)).  ``pooled(t) -> [n_idx, H]`` is
+        scatter(t, idx, reduce='max') of a layer output t, which nothing here holds beyond the next layer."""
+        pr, Np = self.precision, x.shape[0]
+        h = g['fc_pos'](Np, [x], precision=pr)                                # fc_pos(pts)
+        x = g['fc1'](Np, [h], relu_in=True, precision=pr)                     # fc1(relu(.))
+        pool = pooled(x)
+        for name in self.LAYERS[2:5]:
+            x = g[name](Np, [x, pool], idxs=[None, idx32], relu_in=True, precision=pr)   # fcK(relu(cat(x, pool[idx])))
+            pool = pooled(x)
+        return g['fc_out'](n_idx, [pool], relu_in=True, precision=pr), h
 
     def forward(self, pts, idx, n_idx):
         if not pts.is_cuda:
@@ -144,35 +169,18 @@ class PointNet(nn.Module):
         self._dev = dev = pts.device
         g = self._cache.get(self._build, dev)
         lib = _lib.load()
-        pr = self.precision
         pts = pts.contiguous().float()
-        Np, H = pts.shape[0], self.hidden_dim
+        n_idx, H = int(n_idx), self.hidden_dim
         idx32 = idx.to(torch.int32).contiguous()
         stream = _lib.stream_ptr(dev)
-
-        # Max-pool over the points of a voxel (scatter(x, idx, reduce='max'), :131,135,139): the rows are grouped by voxel once
-        # (device radix sort -> row list + offsets), each layer's stored output is then reduced per voxel by
-        # v3d_segment_max_f32 -- no atomics (the gather-GEMM's fused scatter-max was 80 % of a layer's time; csrc/segment.hip).
-        perm = torch.empty(Np, dtype=torch.int32, device=dev)
-        offs = torch.empty(n_idx + 1, dtype=torch.int32, device=dev)
-        wb = lib.v3d_segment_csr_workspace_bytes(Np)
-        ws = self._ws.get('segcsr', wb, dev)
-        _lib.check(lib.v3d_segment_csr(idx32.data_ptr(), Np, int(n_idx), perm.data_ptr(), offs.data_ptr(), ws.data_ptr(),
-                                       ws.numel(), stream), 'v3d_segment_csr')
+        perm, offs = self._segments(idx32, n_idx, dev)
 
         def pooled(x):
             pool = torch.empty((n_idx, H), dtype=torch.float32, device=dev)
-            _lib.check(lib.v3d_segment_max_f32(x.data_ptr(), x.stride(0), perm.data_ptr(), offs.data_ptr(), int(n_idx), H,
+            _lib.check(lib.v3d_segment_max_f32(x.data_ptr(), x.stride(0), perm.data_ptr(), offs.data_ptr(), n_idx, H,
                                                pool.data_ptr(), H, stream), 'v3d_segment_max_f32')
             return pool
-
-        h = g['fc_pos'](Np, [pts], precision=pr)                              # fc_pos(pts)
-        x = g['fc1'](Np, [h], relu_in=True, precision=pr)                     # fc1(relu(.))
-        pool = pooled(x)
-        for name in ('fc2', 'fc3', 'fc4'):
-            x = g[name](Np, [x, pool], idxs=[None, idx32], relu_in=True, precision=pr)   # fcK(relu(cat(x, pool[idx])))
-            pool = pooled(x)
-        return g['fc_out'](n_idx, [pool], relu_in=True, precision=pr)
+        return self._layers(g, pts, idx32, n_idx, pooled)[0]
 
 
 class _SparseConv(nn.Module):

@@ -44,7 +44,7 @@ GroupNorm, ReLU, the residual add and the 1x1 ``feat_adj`` are stock differentia
 The producer of F is PointNet (``mv3d/subnetworks/scenemodeling.py:116-144``).  Its stock graph keeps ``cat(x, pool[idx])``
 [Np, 2H] three times, sums the pooled gradients with ``index_add`` atomics and, with torch's ``scatter_reduce('amax')``, splits a
 gradient among equal values where ``torch_scatter`` hands it to one row.  Here it is one node over three streaming kernels
-(``csrc/segment_backward.hip``: ``v3d_segment_max_arg_f32``, ``v3d_segment_sum_f32``, ``v3d_pointnet_pool_backward_f32``; no atomics,
+(``csrc/segment.hip``, beside the forward's pooling: ``v3d_segment_max_arg_f32``, ``v3d_segment_sum_f32``, ``v3d_pointnet_pool_backward_f32``; no atomics,
 bitwise reproducible) and ``torch.mm``:
 
   * ``PointNetFunction`` / ``pointnet``                  ``PointNet.forward`` (the same bits) -> x and the twelve parameters;
@@ -503,9 +503,6 @@ def sparse_unet(unet, feats, xs):
     return out
 
 
-_POINTNET_LAYERS = ('fc_pos', 'fc1', 'fc2', 'fc3', 'fc4', 'fc_out')
-
-
 class PointNetFunction(torch.autograd.Function):
     """``PointNet.forward`` (scenemodeling.py:127-144) as ONE node with the gradients to ``x`` and to the twelve parameters
     (DESIGN.md 4.1f).  The forward is the inference forward call for call in ``pn.precision`` (the same bits), with
@@ -525,34 +522,23 @@ class PointNetFunction(torch.autograd.Function):
         dev = x.device
         pn._dev = dev
         g = pn._cache.get(pn._build, dev)
-        pr = pn.precision
         xc = x.detach().contiguous().float()
-        Np, H = xc.shape[0], pn.hidden_dim
+        H = pn.hidden_dim
+        xs, pools, args = [], [], []
         with torch.cuda.device(dev):
             stream = _lib.stream_ptr(dev)
-            perm = torch.empty(Np, dtype=torch.int32, device=dev)
-            offs = torch.empty(n_idx + 1, dtype=torch.int32, device=dev)
-            ws = pn._ws.get('segcsr', lib.v3d_segment_csr_workspace_bytes(Np), dev)
-            _lib.check(lib.v3d_segment_csr(idx32.data_ptr(), Np, n_idx, perm.data_ptr(), offs.data_ptr(), ws.data_ptr(), ws.numel(),
-                                           stream), 'v3d_segment_csr')
+            perm, offs = pn._segments(idx32, n_idx, dev)
 
             def pooled(t):
                 pool = torch.empty((n_idx, H), dtype=torch.float32, device=dev)
                 arg = torch.empty((n_idx, H), dtype=torch.int32, device=dev)
                 _lib.check(lib.v3d_segment_max_arg_f32(t.data_ptr(), t.stride(0), perm.data_ptr(), offs.data_ptr(), n_idx, H,
                                                        pool.data_ptr(), H, arg.data_ptr(), H, stream), 'v3d_segment_max_arg_f32')
-                return pool, arg
-
-            h0 = g['fc_pos'](Np, [xc], precision=pr)
-            xs = [g['fc1'](Np, [h0], relu_in=True, precision=pr)]
-            pools, args = [], []
-            for name in ('fc2', 'fc3', 'fc4', None):
-                pool, arg = pooled(xs[-1])
+                xs.append(t)
                 pools.append(pool)
                 args.append(arg)
-                if name is not None:
-                    xs.append(g[name](Np, [xs[-1], pool], idxs=[None, idx32], relu_in=True, precision=pr))
-            out = g['fc_out'](n_idx, [pools[-1]], relu_in=True, precision=pr)
+                return pool
+            out, h0 = pn._layers(g, xc, idx32, n_idx, pooled)
         if trace is not None:
             trace.update(h0=h0, **{'x%d' % (i + 1): t for i, t in enumerate(xs)}, **{'pool%d' % (i + 1): t for i, t in enumerate(pools)},
                          **{'arg%d' % (i + 1): t for i, t in enumerate(args)})
@@ -565,7 +551,7 @@ class PointNetFunction(torch.autograd.Function):
         saved = ctx.saved_tensors
         x, h0, xs, pools, args = saved[0], saved[1], saved[2:6], saved[6:10], saved[10:14]
         idx32, perm, offs = saved[14:17]
-        W = saved[17::2]                                        # the six weights, in the order of _POINTNET_LAYERS
+        W = saved[17::2]                                        # the six weights, in the order of PointNet.LAYERS
         need_x, need = ctx.needs_input_grad[4], ctx.needs_input_grad[5:]
         wants = [need[2 * i] or need[2 * i + 1] for i in range(6)]
         # the chain runs down to the lowest layer anybody asks about (x lies below fc_pos)
@@ -633,7 +619,7 @@ def pointnet(pn, x, idx, n_idx, trace=None):
     128."""
     mvsnet._require_cuda(x, 'training.pointnet')
     assert x.dim() == 2 and idx.shape == (x.shape[0],)
-    params = [p for name in _POINTNET_LAYERS for p in (getattr(pn, name).weight, getattr(pn, name).bias)]
+    params = [p for name in pn.LAYERS for p in (getattr(pn, name).weight, getattr(pn, name).bias)]
     return PointNetFunction.apply(pn, trace, idx.to(torch.int32).contiguous(), int(n_idx), x, *params)
 
 

@@ -414,7 +414,9 @@ int v3d_sparse_interp_backward_f32(const void* table, int n_in, int C, int tenso
 /* Row B4's max-pooling over the points of a voxel (scenemodeling.py:129-141, torch_scatter.scatter(reduce='max')) without
  * atomics: v3d_segment_csr groups the rows by segment id once (perm [n]: row indices sorted by id, stable; offsets [n_seg+1]),
  * v3d_segment_max_f32 reduces every segment's rows of src [n, ld] to out [n_seg, ld_out] (first N columns; an empty segment
- * yields -inf, the initial value of the atomic version's pool).  Ids must lie in [0, n_seg). */
+ * yields -inf, the initial value of the atomic version's pool).  Ids must lie in [0, n_seg).  N a multiple of 4 up to 256, ld
+ * and ld_out multiples of 4 and >= N (else V3D_ERR_BAD_SHAPE); src and out 16-byte aligned, as its siblings below require (it
+ * reads and writes 16 bytes per lane as they do): V3D_ERR_BAD_ARG for a null pointer or a misaligned matrix. */
 size_t v3d_segment_csr_workspace_bytes(int n);
 int v3d_segment_csr(const int32_t* seg_id, int n, int n_seg, int32_t* perm, int32_t* offsets, void* workspace,
                     size_t workspace_bytes, void* stream);
@@ -422,8 +424,8 @@ int v3d_segment_max_f32(const float* src, int ld, const int32_t* perm, const int
                         int ld_out, void* stream);
 /* The backward of that pooling and of PointNet's cat(x, pool[idx]) (training; additive within ABI version 9).
  * All three read whole rows 16 bytes per lane through perm / offsets of v3d_segment_csr (or seg_id itself), use no scratch
- * buffer, no LDS and no float atomics, and return the same bits in every call.  Shapes as v3d_segment_max_f32: N a multiple of
- * 4 up to 256, every ld a multiple of 4 and >= N; in addition every matrix must be 16-byte aligned.  Of an output's rows the
+ * buffer, no LDS and no float atomics, and return the same bits in every call.  Shapes and alignment as v3d_segment_max_f32: N a
+ * multiple of 4 up to 256, every ld a multiple of 4 and >= N, every matrix 16-byte aligned.  Of an output's rows the
  * first N columns are written, EVERY one of them; columns behind N and rows behind the last are never touched.
  * Errors, before anything is enqueued: V3D_ERR_BAD_ARG for a null pointer or a misaligned matrix, V3D_ERR_BAD_SHAPE otherwise.
  *   v3d_segment_max_arg_f32  out as v3d_segment_max_f32 (the same bits for every input without NaN) and arg [n_seg, ld_arg]

@@ -110,6 +110,7 @@ def test_segment_max_arg(N, kind, cuda):
     out, arg = poisoned(N_SEG, N, torch.float32, cuda), poisoned(N_SEG, N, torch.int32, cuda)
     libm.check(lib.v3d_segment_max_arg_f32(src.data_ptr(), N + 4, perm.data_ptr(), offs.data_ptr(), N_SEG, N, out.data_ptr(), N + 8,
                                            arg.data_ptr(), N + 8, libm.stream_ptr(cuda)), 'v3d_segment_max_arg_f32')
+    assert untouched(want, N_SEG, N)
     assert untouched(out, N_SEG, N) and untouched(arg, N_SEG, N)
     assert torch.equal(out[:N_SEG, :N], want[:N_SEG, :N])
     ref = pbo.lowest_row_argmax(x, ids, N_SEG)
@@ -218,6 +219,10 @@ def test_entry_points_reject_bad_arguments(cuda):
     st = libm.stream_ptr(cuda)
     P = lambda t: t.data_ptr()
     BAD_SHAPE, BAD_ARG = -1, -2
+    assert lib.v3d_segment_max_f32(P(f), N, None, P(offs), N_SEG, N, P(o), N, st) == BAD_ARG
+    assert lib.v3d_segment_max_f32(P(f) + 4, N, P(perm), P(offs), N_SEG, N, P(o), N, st) == BAD_ARG
+    assert lib.v3d_segment_max_f32(P(f), N, P(perm), P(offs), N_SEG, 30, P(o), N, st) == BAD_SHAPE
+    assert lib.v3d_segment_max_f32(P(f), N, P(perm), P(offs), N_SEG, N, P(o), N - 4, st) == BAD_SHAPE
     assert lib.v3d_segment_max_arg_f32(P(f), N, P(perm), P(offs), N_SEG, N, P(o), N, None, N, st) == BAD_ARG
     assert lib.v3d_segment_max_arg_f32(P(f), N, P(perm), P(offs), N_SEG, 30, P(o), N, P(a), N, st) == BAD_SHAPE
     assert lib.v3d_segment_max_arg_f32(P(f), N, P(perm), P(offs), N_SEG, N, P(o), N, P(a), N - 4, st) == BAD_SHAPE

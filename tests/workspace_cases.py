@@ -291,7 +291,7 @@ CASES.append(Case(
 # ---- v3d_segment_csr -> v3d_segment_max_f32 ---------------------------------------------------------------------------------------
 
 def _segment_make(size):
-    n, n_seg, N = {'small': (700, 300, 40), 'big': (1500, 650, 40)}[size]       # N <= 128: 8 segments per workgroup (segment.hip:101)
+    n, n_seg, N = {'small': (700, 300, 40), 'big': (1500, 650, 40)}[size]       # N <= 128: 8 segments per workgroup (segment.hip:178)
     rng = np.random.default_rng(10 + n)
     ids = rng.integers(0, n_seg, n)
     ids[ids % 5 == 0] += 1                                                     # every fifth segment has no rows
@@ -327,8 +327,8 @@ CASES.append(Case(
     bound='stable argsort / bincount / maximum.at, exact (the scatter-max of oracle.scene.pointnet is exact too)',
     sections=lambda lib, i: {'segcsr': lib.v3d_segment_csr_workspace_bytes(i['n'])},
     groups=lambda i: [('iota_kernel', i['n'], 256), ('segment_offsets_kernel', i['n_seg'] + 1, 256), ('segment_max_kernel<32>', i['n_seg'], 8)],
-    constants=(('iota_kernel<<<(n + 255) / 256, 256', 'segment.hip:83'), ('segment_offsets_kernel<<<(n_seg + 1 + 255) / 256, 256', 'segment.hip:89'),
-               ('segment_max_kernel<32><<<(n_seg + 7) / 8, 256', 'segment.hip:101')), paired=True))
+    constants=(('iota_kernel<<<(n + 255) / 256, 256', 'segment.hip:212'), ('segment_offsets_kernel<<<(n_seg + 1 + 255) / 256, 256', 'segment.hip:218'),
+               ('if (N <= 128) kernel32<<<(rows + 7) / 8, 256', 'segment.hip:178')), paired=True))
 
 
 # ---- v3d_voxel_keys -> v3d_sort_unique_u64 -> v3d_lower_bound_u64 -> v3d_voxel_decode -> v3d_voxelize_status ------------------------
